@@ -9,7 +9,7 @@ index ranges with no data-path collective (weak scaling); the only collectives o
 timing barrier and a MAX over ranks.  `--workload uniq` adds the one real exchange of the path: the
 hash-range all-to-all of circkit_amd/uniq.py over RCCL, inside the timed step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts its own ranks: the parent -- which
@@ -28,6 +28,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+DUMP_LIMIT = 60 << 20    # --dump-outputs: bytes of all .npy files of a run together (every rank's), under 64 MB however counted
+DUMP_RECORDS = 65536     # --dump-outputs: records in the seeded sample at most (fewer when their canonical bytes would not fit)
 
 
 def pmc_traffic(workload):
@@ -111,9 +113,15 @@ def main():
     ap.add_argument("--workload", default="canonicalize", choices=["canonicalize", "uniq", "mixed"],
                     help="canonicalize = BASELINE configs[1] (the headline metric); uniq = configs[2] (50 %% rotational/"
                          "strand duplicates, hash + first-seen); mixed = configs[3] (1M records, L ~ 1/L on [200, 20000])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all): a fixed, seeded sample of records -- canonical bytes, XXH3, first-seen, keep -- so that two builds "
+                         "can be compared output for output (the inputs are seeded too)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     force_dist = os.environ.get("CIRCKIT_BENCH_FORCE_DIST") == "1"   # rehearse the launcher + RCCL path on one GPU
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or force_dist):
         sys.exit(self_launch(args.gpus))           # before anything of torch / HIP is loaded in this process
@@ -260,6 +268,11 @@ def main():
         unprocessed = ln["ctx"].batch_status()
         if unprocessed:
             raise SystemExit("%d records were not processed" % unprocessed)
+    dumped = None
+    if args.dump_outputs:
+        # the lane of the last timed step; nothing has touched its buffers since (the copy yardstick and other_workloads come later)
+        dumped = dump_outputs(np, torch, args.dump_outputs, lanes[(counter[0] - 1) % S], d_off, N, rank, world,
+                              want_bytes=not ((args.workload == "uniq" or args.with_hash) and args.hash_only))
     unique_global = None
     if args.workload == "uniq":
         for ln in lanes:
@@ -382,6 +395,8 @@ def main():
         }
         if unique_global is not None:
             result["unique_records"] = unique_global
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if args.workload == "uniq" and world > 1:
             result["uniq_job_check"] = uniq_job_check
         args._state_hash = state["hash"]
@@ -411,6 +426,45 @@ def main():
         dist.destroy_process_group()
     for ln in lanes:
         ln["ctx"].close()
+
+
+def dump_outputs(np, torch, out_dir, lane, d_off, N, rank, world, want_bytes):
+    """--dump-outputs: what the timed path's last step handed its caller, on a sample of records drawn with a fixed seed, so
+    that the same arguments dump the same records at every run.  Arrays (one row per sampled record, ascending index):
+    sample_records (batch index), sample_lengths, canonical_bytes (the sampled records' canonical forms back to back, as
+    float32 symbol codes), and with the hash xxh3_hi32 / xxh3_lo32 (the two halves of the u64, exact in float64), first_seen,
+    keep.  At --gpus > 1 every rank writes its own shard's files, named <name>_rank<r>.npy.  Returns the file names."""
+    dev = d_off.device
+    budget = DUMP_LIMIT // world - 48 * DUMP_RECORDS            # bytes left for canonical_bytes after the per-record arrays
+    rng = np.random.default_rng(12345 + rank)
+    idx = np.sort(rng.choice(N, size=min(N, DUMP_RECORDS), replace=False)).astype(np.int64)
+    t_idx = torch.from_numpy(idx).to(dev)
+    starts = d_off[t_idx].cpu().numpy()
+    lens = d_off[t_idx + 1].cpu().numpy() - starts
+    if want_bytes:
+        # records in the seeded draw's own order until the budget is spent, so that the kept set does not lean to low indices
+        order = rng.permutation(idx.size)
+        fits = np.cumsum(lens[order] * 4) <= budget
+        sel = np.sort(order[fits])
+        idx, starts, lens, t_idx = idx[sel], starts[sel], lens[sel], t_idx[torch.from_numpy(sel).to(dev)]
+    arrays = {"sample_records": idx.astype(np.float64), "sample_lengths": lens.astype(np.float64)}
+    if want_bytes:
+        first = np.repeat(starts - (np.cumsum(lens) - lens), lens)      # byte j of the dump -> its byte in the batch
+        pos = torch.from_numpy(first + np.arange(first.size, dtype=np.int64)).to(dev)
+        arrays["canonical_bytes"] = lane["out"][pos].cpu().numpy().astype(np.float32)
+    if lane["hash"] is not None:
+        h = lane["hash"][t_idx].cpu().numpy().view(np.uint64)
+        arrays["xxh3_hi32"] = (h >> np.uint64(32)).astype(np.float64)
+        arrays["xxh3_lo32"] = (h & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        arrays["first_seen"] = lane["fs"][t_idx].cpu().numpy().astype(np.float64)
+        arrays["keep"] = lane["keep"][t_idx].cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for name, a in arrays.items():
+        fn = name + (".npy" if world == 1 else "_rank%d.npy" % rank)
+        np.save(os.path.join(out_dir, fn), a)
+        names.append(fn)
+    return names
 
 
 def job_oracle_slice(np, torch, args, N, L, rank, d_bytes, state, keys):

@@ -10,7 +10,7 @@
  * multiple_sequences,multiple_sequences_split_lines,rna_input,repeated,compressed_*});
  * see tests/test_oracle_golden.py.  The reference is Rust and cannot be built in this
  * image (no cargo/rustc), so there is no oracle/_ref build.  Third-party arithmetic
- * that is not under /root/reference is restated from the published algorithm of the
+ * that is not in the reference's own sources is restated from the published algorithm of the
  * pinned crate version:
  *   bio 1.3.1        alphabets::dna::revcomp     (call site lib/src/canonicalize.rs:56)
  *   needletail 0.5.1 sequence::normalize(_,false) (call sites src/canonicalize.rs:24, src/uniq.rs:35)

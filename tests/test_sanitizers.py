@@ -7,7 +7,9 @@
   * the CPU emulator of the kernel source (tests/emu) is ALWAYS built with -fsanitize=undefined,bounds without recovery, so
     every run of tests/test_emu_kernel.py is a UBSan run; here only that the instrumentation is really in the library."""
 import os
+import platform
 import random
+import shutil
 import struct
 import subprocess
 
@@ -134,7 +136,12 @@ def test_sub_range_parse_under_tsan(fasta_tsan, tmp_path):
         f.write(struct.pack("<I", len(cases)))
         for t in cases:
             f.write(struct.pack("<BBI", 1, 1, len(t)) + t)
-    r = subprocess.run([fasta_tsan, str(path)], capture_output=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    # without address randomisation (setarch -R, this process only): this TSan runtime aborts with "unexpected memory mapping"
+    # when the kernel places the program or its libraries outside the layout it was built for, as kernels with 32 bits of
+    # mmap randomisation do; newer TSan runtimes re-execute themselves this way
+    setarch = shutil.which("setarch")
+    cmd = ([setarch, platform.machine(), "-R"] if setarch else []) + [fasta_tsan, str(path)]
+    r = subprocess.run(cmd, capture_output=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
     assert r.returncode == 0 and r.stderr == b"", r.stderr.decode(errors="replace")[-3000:]
 
 

@@ -92,7 +92,9 @@ def _worker(rank, world, port, hashes, cuts, q, exchange, rows_table=False):
     if rows_table:
         assert table.partitioned and table.gathered            # the device-rows branch really ran
     q.put((rank, fs.numpy(), keep.numpy()))
-    dist.barrier()
+    # gloo's own barrier: dist.barrier() asks torch which accelerator the machine has, and on a GPU box that opens the
+    # device in every rank of this CPU test
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -173,7 +175,7 @@ def _job_worker(rank, world, port, n, length, q, broken):
         fs, keep = uniq.first_seen(RowsTable(), hashes, base_index=rank * n, exchange="partition")
     wrong, cross, distinct, _ = W.job_check(fs, keep, n, length, world, rank, dev)
     q.put((rank, wrong, cross, distinct, int(keep.sum())))
-    dist.barrier()
+    dist.monitored_barrier()            # (not dist.barrier(): see _worker)
     dist.destroy_process_group()
 
 
