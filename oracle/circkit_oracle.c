@@ -142,16 +142,31 @@ void ck_oracle_revcomp(const uint8_t *s, size_t n, uint8_t *out)
 }
 
 /* canonicalize -- lib/src/canonicalize.rs:54-63.
- * a = lmsr(s); b = lmsr(revcomp(a)); return a if a < b else b (slice order: unsigned bytes). */
+ * a = lmsr(s); b = lmsr(revcomp(a)); return a if a < b else b (slice order: unsigned bytes).
+ * canon_rec is the one restatement, with the caller's scratch (a, rc, b: n bytes each): it also returns which of the two
+ * the reference returns (*strand: 0 = a, 1 = b) and the index of the lmsr that produced it (lmsr_index(s), or
+ * lmsr_index(revcomp(a))) -- the definition tests/seqsets.py::expected and include/circkit.h give. */
+static void canon_rec(const uint8_t *s, size_t n, uint8_t *out, uint8_t *a, uint8_t *rc, uint8_t *b,
+                      uint32_t *index, uint8_t *strand)
+{
+    size_t i = ck_oracle_lmsr_index(s, n);   /* :55 */
+    memcpy(a, s + i, n - i);
+    memcpy(a + (n - i), s, i);
+    ck_oracle_revcomp(a, n, rc);             /* :56 */
+    size_t j = ck_oracle_lmsr_index(rc, n);  /* :56 */
+    memcpy(b, rc + j, n - j);
+    memcpy(b + (n - j), rc, j);
+    const int fwd = memcmp(a, b, n) < 0;     /* :58-61 (n == 0: equal, b returned) */
+    if (out) memcpy(out, fwd ? a : b, n);
+    if (index) *index = (uint32_t)(fwd ? i : j);
+    if (strand) *strand = fwd ? 0 : 1;
+}
+
 void ck_oracle_canonicalize(const uint8_t *s, size_t n, uint8_t *out)
 {
     if (n == 0) return;
     uint8_t *a = (uint8_t *)malloc(n), *rc = (uint8_t *)malloc(n), *b = (uint8_t *)malloc(n);
-    ck_oracle_lmsr(s, n, a);                 /* :55 */
-    ck_oracle_revcomp(a, n, rc);             /* :56 */
-    ck_oracle_lmsr(rc, n, b);                /* :56 */
-    if (memcmp(a, b, n) < 0) memcpy(out, a, n);   /* :58-59 */
-    else memcpy(out, b, n);                       /* :60-61 */
+    canon_rec(s, n, out, a, rc, b, NULL, NULL);
     free(a); free(rc); free(b);
 }
 
@@ -318,7 +333,7 @@ uint64_t ck_oracle_xxh3_64(const uint8_t *in, size_t len)
  * of the reference's --threads worker pool (src/canonicalize.rs:19).
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
-    const uint8_t *bytes; const uint64_t *off; uint8_t *out; uint64_t *hash;
+    const uint8_t *bytes; const uint64_t *off; uint8_t *out; uint64_t *hash; uint32_t *index; uint8_t *strand;
     uint64_t lo, hi;
     int nth;                                          /* the quadratic cost model instead of the linear transcription */
 } job_t;
@@ -326,38 +341,53 @@ typedef struct {
 static void *batch_worker(void *arg)
 {
     job_t *j = (job_t *)arg;
+    size_t cap = 0;
+    uint8_t *scratch = NULL;                          /* a, rc, b of canon_rec + the canonical form when out is NULL */
     for (uint64_t i = j->lo; i < j->hi; ++i) {
         uint64_t o = j->off[i], n = j->off[i + 1] - o;
         if (j->nth) {
             canonicalize_nth(j->bytes + o, n, j->out + o);
-        } else if (j->out) {
-            ck_oracle_canonicalize(j->bytes + o, n, j->out + o);
-            if (j->hash) j->hash[i] = ck_oracle_xxh3_64(j->out + o, n);
-        } else if (j->hash) {
-            uint8_t *tmp = (uint8_t *)malloc(n ? n : 1);
-            ck_oracle_canonicalize(j->bytes + o, n, tmp);
-            j->hash[i] = ck_oracle_xxh3_64(tmp, n);
-            free(tmp);
+            continue;
         }
+        if (4 * n + 4 > cap) {
+            cap = 4 * n + 4 > 2 * cap ? 4 * n + 4 : 2 * cap;
+            free(scratch);
+            scratch = (uint8_t *)malloc(cap);
+        }
+        uint8_t *a = scratch, *rc = scratch + n, *b = scratch + 2 * n;
+        uint8_t *c = j->out ? j->out + o : (j->hash ? scratch + 3 * n : NULL);
+        canon_rec(j->bytes + o, n, c, a, rc, b, j->index ? j->index + i : NULL, j->strand ? j->strand + i : NULL);
+        if (j->hash) j->hash[i] = ck_oracle_xxh3_64(c, n);
     }
+    free(scratch);
     return NULL;
 }
 
 static void canonicalize_batch(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records,
-                               uint8_t *out_bytes, uint64_t *out_xxh3, int threads, int nth);
+                               uint8_t *out_bytes, uint64_t *out_xxh3, uint32_t *out_index, uint8_t *out_strand,
+                               int threads, int nth);
 void ck_oracle_canonicalize_batch(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records,
                                   uint8_t *out_bytes, uint64_t *out_xxh3, int threads)
 {
-    canonicalize_batch(bytes, offsets, n_records, out_bytes, out_xxh3, threads, 0);
+    canonicalize_batch(bytes, offsets, n_records, out_bytes, out_xxh3, NULL, NULL, threads, 0);
+}
+/* the same with the rotation index and the strand per record (what the product's d_out_index / d_out_strand hold,
+ * include/circkit.h); every output nullable */
+void ck_oracle_canonicalize_batch_aux(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records,
+                                      uint8_t *out_bytes, uint64_t *out_xxh3, uint32_t *out_index, uint8_t *out_strand,
+                                      int threads)
+{
+    canonicalize_batch(bytes, offsets, n_records, out_bytes, out_xxh3, out_index, out_strand, threads, 0);
 }
 /* the same batch through the quadratic cost model (out_bytes required) */
 void ck_oracle_canonicalize_batch_nth(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records,
                                       uint8_t *out_bytes, int threads)
 {
-    canonicalize_batch(bytes, offsets, n_records, out_bytes, NULL, threads, 1);
+    canonicalize_batch(bytes, offsets, n_records, out_bytes, NULL, NULL, NULL, threads, 1);
 }
 static void canonicalize_batch(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records,
-                               uint8_t *out_bytes, uint64_t *out_xxh3, int threads, int nth)
+                               uint8_t *out_bytes, uint64_t *out_xxh3, uint32_t *out_index, uint8_t *out_strand,
+                               int threads, int nth)
 {
     comp_init();
     if (threads < 1) threads = 1;
@@ -366,6 +396,7 @@ static void canonicalize_batch(const uint8_t *bytes, const uint64_t *offsets, ui
     job_t *jobs = (job_t *)malloc(sizeof(job_t) * threads);
     for (int t = 0; t < threads; ++t) {
         jobs[t].bytes = bytes; jobs[t].off = offsets; jobs[t].out = out_bytes; jobs[t].hash = out_xxh3; jobs[t].nth = nth;
+        jobs[t].index = out_index; jobs[t].strand = out_strand;
         jobs[t].lo = n_records * t / threads; jobs[t].hi = n_records * (t + 1) / threads;
         if (threads == 1) batch_worker(&jobs[t]);
         else pthread_create(&tid[t], NULL, batch_worker, &jobs[t]);

@@ -48,6 +48,7 @@ def lib():
         L.ck_oracle_xxh3_64.restype = ctypes.c_uint64
         L.ck_oracle_xxh3_64.argtypes = [u8p, ctypes.c_size_t]
         L.ck_oracle_canonicalize_batch.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, u64p, ctypes.c_int]
+        L.ck_oracle_canonicalize_batch_aux.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, u64p, u8p, u8p, ctypes.c_int]
         L.ck_oracle_canonicalize_batch_nth.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, ctypes.c_int]
         L.ck_oracle_lmsr_index_nth.restype = ctypes.c_size_t
         L.ck_oracle_lmsr_index_nth.argtypes = [u8p, ctypes.c_size_t]
@@ -136,6 +137,23 @@ def canonicalize_batch(bytes_arr, offsets, want_bytes=True, want_hash=False, thr
         hs.ctypes.data if hs is not None else None, int(threads))
     return (out[:len(bytes_arr)] if out is not None else None,
             hs[:n] if hs is not None else None)
+
+
+def canonicalize_batch_aux(bytes_arr, offsets, want_bytes=True, want_hash=False, want_index=True, want_strand=True, threads=1):
+    """canonicalize_batch plus the rotation index (uint32) and the strand (uint8) of every record, as the product's
+    d_out_index / d_out_strand define them (tests/seqsets.py::expected).  Returns (out_bytes, hashes, index, strand), each
+    None when not wanted."""
+    bytes_arr = np.ascontiguousarray(bytes_arr, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.empty(max(len(bytes_arr), 1), dtype=np.uint8) if want_bytes else None
+    hs = np.empty(max(n, 1), dtype=np.uint64) if want_hash else None
+    idx = np.empty(max(n, 1), dtype=np.uint32) if want_index else None
+    st = np.empty(max(n, 1), dtype=np.uint8) if want_strand else None
+    lib().ck_oracle_canonicalize_batch_aux(
+        bytes_arr.ctypes.data if len(bytes_arr) else None, offsets.ctypes.data, n,
+        *[a.ctypes.data if a is not None else None for a in (out, hs, idx, st)], int(threads))
+    return (out[:len(bytes_arr)] if out is not None else None,) + tuple(a[:n] if a is not None else None for a in (hs, idx, st))
 
 
 def uniq_first_seen(hashes):

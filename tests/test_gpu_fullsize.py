@@ -1,13 +1,17 @@
 """GPU tests at BASELINE.json's full sizes (configs 3 and 4), of the per-batch build selection, and of the multi-GPU
 `uniq` exchange over RCCL (backend nccl, rehearsed at world size 1 on the box's one GPU).  Run on a real MI355X:
 pytest -m gpu.  Full-size checks use the size-independent properties of the canonical form (idempotence, rotation and
-strand invariance, the expected number of distinct records) plus the oracle on a slice, as SURVEY.md 8(d) prescribes."""
+strand invariance, the expected number of distinct records) plus the oracle on a slice, as SURVEY.md 8(d) prescribes, and
+then the oracle on EVERY record (tests/fullcheck.py walks the batch in chunks): agreement between builds and invariance
+cannot see an error all builds share, e.g. a byte offset truncated past 2^32."""
 import os
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from tests import fullcheck
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,7 +37,8 @@ def ctx():
 def test_uniq_config3_full_size(ctx, O):
     """BASELINE configs[2] as bench.py generates it: 10M x 1 kb, half of the records rotated / reverse-complemented
     copies of the other half, shuffled.  Exactly 5,000,000 records survive; first-seen indices of the first 100k
-    records equal the oracle's on the oracle's own hashes of that sample (SURVEY.md 8d cfg 3)."""
+    records equal the oracle's on the oracle's own hashes of that sample (SURVEY.md 8d cfg 3); then bytes, hashes and first-seen
+of all 10M records against the oracle (first-seen over the oracle's hashes of the whole batch)."""
     import torch
     from circkit_amd import uniq, workloads as W
     N, L = 10_000_000, 1000
@@ -51,12 +56,14 @@ def test_uniq_config3_full_size(ctx, O):
     # a record is kept iff nothing before it has its hash, and every record points at a kept one with the same hash
     assert bool((fs <= torch.arange(N, device=dev)).all())
     assert bool(keep[fs].all()) and bool((hs[fs] == hs).all())
+    # a quick slice first; the fullcheck.check_batch call below compares every record of the same outputs
     S = 100_000
     h_off = np.arange(S + 1, dtype=np.uint64) * np.uint64(L)
     exp, exp_h = O.canonicalize_batch(x[:S * L].cpu().numpy(), h_off, True, True, threads=8)
     assert np.array_equal(out[:S * L].cpu().numpy(), exp)
     assert np.array_equal(hs[:S].cpu().numpy().astype(np.uint64), exp_h)
     assert np.array_equal(fs[:S].cpu().numpy().astype(np.uint64), O.uniq_first_seen(exp_h))
+    print("full check:", fullcheck.check_batch(O, x, off, N, out_bytes=out, out_xxh3=hs, first_seen=fs))
     # hash-only mode (uniq without --canonicalize) gives the same hashes without an output buffer
     hs2 = torch.empty_like(hs)
     ctx.canonicalize_batch_device(x, off, N, out_xxh3=hs2)
@@ -68,7 +75,7 @@ def test_uniq_config3_full_size(ctx, O):
 def test_mixed_config4_full_size(ctx, O, n_frac):
     """BASELINE configs[3] at its full 1M records (4.3 Gbases, lengths log-uniform on [200, 20000]), and its 1 % N
     variant: oracle bytes on a 5k-record slice; over all records idempotence and invariance under reverse
-    complement + rotation."""
+    complement + rotation, and the oracle's bytes and hashes."""
     import torch
     from circkit_amd import workloads as W
     N = 1_000_000
@@ -85,6 +92,7 @@ def test_mixed_config4_full_size(ctx, O, n_frac):
     assert ctx.batch_status() == 0
     assert ctx.last_batch_mode() == 3                       # a third of the records are longer than 2032 bases
     assert bool((c1[total:] == 0x3F).all())
+    # a quick slice first; the fullcheck.check_batch calls below compare every record of the same outputs
     S = 5000
     h_off = offs[:S + 1].numpy().astype(np.uint64)
     nb = int(h_off[-1])
@@ -116,10 +124,14 @@ def test_mixed_config4_full_size(ctx, O, n_frac):
     assert torch.equal(h1, h2) and torch.equal(h1, h3)
     _, exp_h = O.canonicalize_batch(x[:nb].cpu().numpy(), h_off, False, True, threads=8)
     assert np.array_equal(h1[:S].cpu().numpy().astype(np.uint64), exp_h)
+    # every record: bytes + hash of the bytes + hash call (c1 of the bytes-only call == c4 and h2 of the hash-only call == h1,
+    # asserted above)
+    print("full check:", fullcheck.check_batch(O, x, off, N, out_bytes=c4, out_xxh3=h1))
 
 
 def test_one_percent_n_headline_shape(ctx, O):
-    """10M x 1 kb with 1 % N (practically every record holds an N): oracle on a slice, idempotence over everything."""
+    """10M x 1 kb with 1 % N (practically every record holds an N): oracle on a slice, then on every record (bytes and
+    XXH3), idempotence over everything."""
     import torch
     from circkit_amd import workloads as W
     N, L = 10_000_000, 1000
@@ -130,10 +142,12 @@ def test_one_percent_n_headline_shape(ctx, O):
     hs = torch.empty(N, dtype=torch.int64, device=dev)
     ctx.canonicalize_batch_device(x, off, N, out_bytes=c1, out_xxh3=hs)
     assert ctx.batch_status() == 0
+    # a quick slice first; the fullcheck.check_batch call below compares every record of the same outputs
     S = 20000
     exp, exp_h = O.canonicalize_batch(x[:S * L].cpu().numpy(), np.arange(S + 1, dtype=np.uint64) * np.uint64(L), True, True, 8)
     assert np.array_equal(c1[:S * L].cpu().numpy(), exp)
     assert np.array_equal(hs[:S].cpu().numpy().astype(np.uint64), exp_h)
+    print("full check:", fullcheck.check_batch(O, x, off, N, out_bytes=c1, out_xxh3=hs))
     c2 = torch.empty_like(x)
     ctx.canonicalize_batch_device(c1, off, N, out_bytes=c2)
     torch.cuda.synchronize()
@@ -292,7 +306,8 @@ def test_config5_rank7_shard(ctx, O):
     1 kb at global record index 87,500,000 (base offsets up to 10^11 in the counter-based generator, 12.5 GB in + 12.5 GB
     out in ONE batch).  Oracle bytes on a 20k slice whose INPUT is regenerated on the host at the same global base (so the
     device generator's 64-bit base arithmetic is pinned too), two slices deep inside the shard, idempotence and invariance
-    under reverse complement + rotation over the whole shard (lib/src/canonicalize.rs:54-63, :124-132, :216-231)."""
+    under reverse complement + rotation over the whole shard (lib/src/canonicalize.rs:54-63, :124-132, :216-231); then the
+    oracle's bytes of every record, on input regenerated on the host for the whole shard."""
     import torch
     from circkit_amd import workloads as W
     N, L, rank = 12_500_000, 1000, 7
@@ -309,6 +324,9 @@ def test_config5_rank7_shard(ctx, O):
         assert np.array_equal(host_in, x[r0 * L:(r0 + 20_000) * L].cpu().numpy()), "device generator differs from the host's at the global base"
         exp, _ = O.canonicalize_batch(host_in, h_off, True, False, threads=8)
         assert np.array_equal(c1[r0 * L:(r0 + 20_000) * L].cpu().numpy(), exp)
+    # every record, its input regenerated on the host chunk by chunk at the shard's global base (pins the device generator
+    # over the whole shard, 12.5 GB)
+    print("full check:", fullcheck.check_batch(O, x, off, N, out_bytes=c1, host_input=fullcheck.synth_input(O, 42, rank * N * L)))
     c2 = torch.empty_like(x)
     ctx.canonicalize_batch_device(c1, off, N, out_bytes=c2)
     assert ctx.batch_status() == 0

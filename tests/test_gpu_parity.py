@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import fullcheck
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -413,7 +415,8 @@ def test_device_generator_matches_host_generator(ctx, O):
 
 def test_full_size_properties_10m_x_1kb(ctx, O):
     """BASELINE config 2 at full size (10M x 1 kb, device resident): idempotence, strand invariance and
-    rotation invariance of the canonical form, plus byte parity with the oracle on a 20k-record slice."""
+    rotation invariance of the canonical form, plus parity with the oracle on a 20k-record slice and then on every
+    record (bytes, XXH3, index, strand; byte offsets up to 10^10, past 2^32)."""
     import torch
     N, L = 10_000_000, 1000
     dev = torch.device("cuda", 0)
@@ -446,6 +449,9 @@ def test_full_size_properties_10m_x_1kb(ctx, O):
     torch.cuda.synchronize()
     assert torch.equal(c0[:N * L], c1[:N * L])
     assert np.array_equal(hs[:S].cpu().numpy().astype(np.uint64), exp_h)
+    # every record against the oracle (tests/fullcheck.py): the aux build's bytes, index and strand, the XXH3 of the uniq
+    # build; the bytes-only and the uniq builds' bytes equal c1 everywhere (asserted above), so they are covered too
+    print("full check:", fullcheck.check_batch(O, x, off, N, out_bytes=c1, out_xxh3=hs, out_index=idx, out_strand=strand))
     del c0, hs
     # idempotence: canonical input -> identical output, rotation index 0 whenever the forward strand is returned
     c2 = torch.empty_like(x)
@@ -959,3 +965,128 @@ def test_batches_of_short_records_bytes_only_pair_build(ctx, O):
             assert ctx.batch_status() == 0 and ctx.last_batch_mode() == 1
             assert np.array_equal(d_out[:len(data)].cpu().numpy(), exp), (len(seqs), rep)
     ctx.use_own_stream()
+
+
+# ---- batches at the streaming launch's geometry edges ----------------------------------------------------------------------
+# launch_canon (circkit_hip.hip) cuts a batch of n records into G workgroups of the streaming kernel (per_step records per
+# iteration: StreamC::GROUP = CK_STREAM_WPB * CK_STREAM_RPW, or StreamCAux::GROUP = WPB * RPW of StreamCfg<4, 4, 2, 1> when
+# index / strand are wanted), G = max(min(ceil(n / per_step), N_CU * CK_FAST_BPC), min(n, N_CU * 16)); the stages that walk
+# all records take all_cap = ceil(n / G) per segment, and when G >= 4096 and all_cap >= 2 << CK_TAPER_GENS the last
+# CK_TAPER_GENS generations of G / CK_TAPER_DIV segments taper off (canon_core.h seg_records) with all_cap raised until they
+# still hold n.  With the constants of this writing (16, 1, 4 * 2 = 8, 256, 128, 3, 16):
+#   G leaves its floor of 4096       n = 65 537 (bytes / + XXH3 / hash only)      n = 32 769 (+ index / strand)
+#   taper starts (all_cap 15 -> 16,  n = 61 441: 4096 segments, all_cap 18      n = 491 521: 32 768 segments, all_cap 18
+#   raised by the taper to 18)
+#   grid capped at 32 768 (one       n = 524 273 (524 288 = 32 768 * 16: every    n = 262 137
+#   workgroup walks several groups)  workgroup exactly one group)
+# _geometry() below restates that arithmetic from the constants in the sources, and the test asserts the counts still sit on
+# both sides of each edge: a change of those constants fails here and points back at this list.
+GEOMETRY_COUNTS = [32_768, 32_769, 61_440, 61_441, 61_442, 65_536, 65_537, 262_136, 262_137, 262_138, 491_520, 491_521, 491_522,
+                   524_272, 524_273, 524_288, 524_289, 1_000_003]
+
+
+def _hip_constants():
+    import re
+    src = os.path.join(os.path.dirname(GOLDEN), os.pardir, "circkit_amd", "csrc")
+    hip = open(os.path.join(src, "circkit_hip.hip")).read() + open(os.path.join(src, "canon_core.h")).read()
+    c = {k: int(re.search(r"#define %s (\d+)" % k, hip).group(1)) for k in ("CK_STREAM_WPB", "CK_STREAM_RPW", "CK_FAST_BPC", "CK_TAPER_GENS",
+                                                                             "CK_TAPER_DIV")}
+    c["N_CU"] = int(re.search(r"constexpr int N_CU = (\d+);", hip).group(1))
+    wpb, _, rpw, _ = map(int, re.search(r"using StreamCAux = ck::StreamCfg<(\d+), (\d+), (\d+), (\d+)>;", hip).groups())
+    c["AUX_GROUP"] = wpb * rpw
+    return c
+
+
+def _geometry(n, aux, c):
+    """(G, all_cap, tapered) of launch_canon for a batch of n records."""
+    per_step = c["AUX_GROUP"] if aux else c["CK_STREAM_WPB"] * c["CK_STREAM_RPW"]
+    G = max(min(-(-n // per_step), c["N_CU"] * c["CK_FAST_BPC"]), min(n, c["N_CU"] * 16))
+    all_cap, gens = -(-n // G), c["CK_TAPER_GENS"]
+    if not (G >= 4096 and all_cap >= 2 << gens):
+        return G, all_cap, False
+    log2 = 0
+    while (2 << log2) <= G // c["CK_TAPER_DIV"]:
+        log2 += 1
+    seg0 = G - gens * (1 << log2)
+    while seg0 * all_cap + (1 << log2) * sum(all_cap >> j for j in range(1, gens + 1)) < n:
+        all_cap += 1
+    return G, all_cap, True
+
+
+def test_geometry_counts_straddle_the_launch_edges():
+    c = _hip_constants()
+    cap = c["N_CU"] * c["CK_FAST_BPC"]
+    for aux in (False, True):
+        for name, edge in (("floor", lambda v: v[0] > 4096), ("taper", lambda v: v[2]), ("grid cap", lambda v: v[0] == cap)):
+            lo, hi = 1, 1 << 22                           # each edge is monotone in n: bisect for the first count past it
+            assert not edge(_geometry(lo, aux, c)) and edge(_geometry(hi, aux, c))
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (mid, hi) if not edge(_geometry(mid, aux, c)) else (lo, mid)
+            assert lo in GEOMETRY_COUNTS and hi in GEOMETRY_COUNTS, (aux, name, hi)
+        G, _, tapered = _geometry(GEOMETRY_COUNTS[-1], aux, c)
+        assert G == cap and tapered
+
+
+@pytest.mark.parametrize("kind", ["mode1_1kb", "short_200b", "mode2_1500b", "mode3_log_uniform_1pct_n"])
+def test_launch_geometry_edges_every_record(O, kind):
+    """Batches of GEOMETRY_COUNTS records (both sides of where the streaming launch's grid leaves its floor, is capped, and where
+    the walking stages' segments start to taper, for the workgroup sizes of both builds) of four kinds of content, each through
+    the four output combinations -- bytes only, bytes + XXH3, bytes + index + strand, hash only -- on one context: every record
+    of every output against the oracle (tests/fullcheck.py), and nothing written outside [offsets[0], offsets[n]) of the byte
+    output or past n of the per-record outputs (0x3F canaries; the payload starts at an odd byte of its buffer)."""
+    import torch
+    import circkit_amd
+    from circkit_amd import workloads as W
+    dev = torch.device("cuda", 0)
+    ctx = circkit_amd.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    lead = 13
+    stats = []
+    for k, n in enumerate(GEOMETRY_COUNTS):
+        g = torch.Generator(device="cpu").manual_seed(1000 + k)
+        if kind == "mode1_1kb":
+            lens = torch.randint(960, 1009, (n,), generator=g)
+        elif kind == "short_200b":
+            lens = torch.full((n,), 200, dtype=torch.int64)
+        elif kind == "mode2_1500b":
+            lens = torch.randint(1450, 1551, (n,), generator=g)
+        else:
+            lens = None
+        if lens is None:
+            offs = W.log_uniform_offsets(n, 2000 + k)
+        else:
+            offs = torch.zeros(n + 1, dtype=torch.int64)
+            offs[1:] = torch.cumsum(lens, 0)
+        total = int(offs[-1])
+        off = (offs + lead).to(dev)
+        x = torch.full((lead + total + 64,), 0x3F, dtype=torch.uint8, device=dev)
+        ctx.synth_fill_device(3000 + k, 0, total, x[lead:])
+        if kind.endswith("1pct_n"):
+            W.sprinkle_n(x[lead:], total, 0.01, 4000 + k, dev)
+        outs = [torch.full_like(x, 0x3F) for _ in range(3)]
+        hs = [torch.full((n + 8,), 0x3F3F3F3F3F3F3F3F, dtype=torch.int64, device=dev) for _ in range(2)]
+        idx = torch.full((n + 8,), 0x3F3F3F3F, dtype=torch.int32, device=dev)
+        st = torch.full((n + 8,), 0x3F, dtype=torch.uint8, device=dev)
+        ctx.canonicalize_batch_device(x, off, n, out_bytes=outs[0])
+        ctx.canonicalize_batch_device(x, off, n, out_bytes=outs[1], out_xxh3=hs[0])
+        ctx.canonicalize_batch_device(x, off, n, out_bytes=outs[2], out_index=idx, out_strand=st)
+        ctx.canonicalize_batch_device(x, off, n, out_xxh3=hs[1])
+        assert ctx.batch_status() == 0, (kind, n)
+        for t in outs:
+            assert bool((t[:lead] == 0x3F).all()) and bool((t[lead + total:] == 0x3F).all()), ("wrote outside the batch", kind, n)
+        for t in hs + [idx, st]:
+            assert bool((t[n:] == t[-1]).all()) and int(t[-1]) in (0x3F3F3F3F3F3F3F3F, 0x3F3F3F3F, 0x3F), ("wrote past n", kind, n)
+        # every output of every call: one oracle pass over the batch with all four outputs; an output that differs from the one
+        # checked gets a pass of its own, which names the first record it has wrong
+        info = fullcheck.check_batch(O, x, off, n, out_bytes=outs[2], out_xxh3=hs[0], out_index=idx, out_strand=st)
+        for t in outs[:2]:
+            if not torch.equal(t, outs[2]):
+                fullcheck.check_batch(O, x, off, n, out_bytes=t)
+                raise AssertionError("output bytes differ outside the records (%s, n=%d)" % (kind, n))
+        if not torch.equal(hs[1], hs[0]):
+            fullcheck.check_batch(O, x, off, n, out_xxh3=hs[1])
+        stats.append((n, info["end_offset"], info["seconds"]))
+        del x, outs, hs, idx, st
+    print(kind, "records, end offset, seconds:", stats)
+    ctx.close()

@@ -208,3 +208,35 @@ def test_synth_fill_is_counter_based():
     assert np.array_equal(a[1234:2234], b)
     assert set(a.tobytes()) == set(b"ACGT")
     assert not np.array_equal(O.synth_fill(43, 0, 100), a[:100])
+
+
+def _aux_sets():
+    from tests import seqsets
+    recs = O.read_fasta(open(os.path.join(GOLDEN, "ref_examples", "nim_cated", "realistic_input.fasta"), "rb").read())
+    sets = {"adversarial": seqsets.adversarial(), "nim_cated": [O.normalize(s)[0] for _, s in recs]}
+    for k, alpha in enumerate((b"ACGT", b"ACGTN", b"ACGTN-", b"AC", b"ACGTRYKMacgtn")):
+        sets["random_" + alpha.decode()] = seqsets.random_mixed(500 + k, 300, 0, 2500, alpha)
+    return sets
+
+
+@pytest.mark.parametrize("name", ["adversarial", "nim_cated", "random_ACGT", "random_ACGTN", "random_ACGTN-", "random_AC",
+                                  "random_ACGTRYKMacgtn"])
+def test_batch_aux_matches_expected_per_record(name):
+    """ck_oracle_canonicalize_batch_aux (the whole-batch checker's index / strand source, tests/fullcheck.py) equals the
+    per-record definition seqsets.expected on every record, and its bytes / hashes equal canonicalize_batch's."""
+    from tests import seqsets
+    seqs = _aux_sets()[name]
+    data, offs = seqsets.pack(seqs)
+    out, hs, idx, st = O.canonicalize_batch_aux(data, offs, True, True, True, True, threads=3)
+    exp, exp_h = O.canonicalize_batch(data, offs, True, True, threads=1)
+    assert np.array_equal(out, exp) and np.array_equal(hs, exp_h)
+    assert idx.dtype == np.uint32 and st.dtype == np.uint8
+    for i, s in enumerate(seqs):
+        c, strand, index = seqsets.expected(O, s)
+        assert out[int(offs[i]):int(offs[i + 1])].tobytes() == c, i
+        assert (int(st[i]), int(idx[i])) == (strand, index), (i, s[:80])
+    # any subset of the outputs, any thread count: the same answers
+    _, _, idx2, st2 = O.canonicalize_batch_aux(data, offs, False, False, True, True, threads=7)
+    assert np.array_equal(idx2, idx) and np.array_equal(st2, st)
+    _, hs2, _, st3 = O.canonicalize_batch_aux(data, offs, False, True, False, True, threads=1)
+    assert np.array_equal(hs2, hs) and np.array_equal(st3, st)
