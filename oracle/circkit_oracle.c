@@ -405,6 +405,45 @@ static void canonicalize_batch(const uint8_t *bytes, const uint64_t *offsets, ui
     free(tid); free(jobs);
 }
 
+/* lmsr -- lib/src/canonicalize.rs:41-47 -- for a whole batch: forward strand only, what the product's
+ * circkit_lmsr_batch_device computes (out_bytes: lmsr(record), out_index: lmsr_index(record); both nullable) */
+typedef struct {
+    const uint8_t *bytes; const uint64_t *off; uint8_t *out; uint32_t *index;
+    uint64_t lo, hi;
+} lmsr_job_t;
+
+static void *lmsr_worker(void *arg)
+{
+    lmsr_job_t *j = (lmsr_job_t *)arg;
+    for (uint64_t i = j->lo; i < j->hi; ++i) {
+        const uint64_t o = j->off[i], n = j->off[i + 1] - o;
+        const size_t k = ck_oracle_lmsr_index(j->bytes + o, n);
+        if (j->out) {
+            memcpy(j->out + o, j->bytes + o + k, n - k);
+            memcpy(j->out + o + (n - k), j->bytes + o, k);
+        }
+        if (j->index) j->index[i] = (uint32_t)k;
+    }
+    return NULL;
+}
+
+void ck_oracle_lmsr_batch(const uint8_t *bytes, const uint64_t *offsets, uint64_t n_records, uint8_t *out_bytes,
+                          uint32_t *out_index, int threads)
+{
+    if (threads < 1) threads = 1;
+    if ((uint64_t)threads > n_records) threads = n_records ? (int)n_records : 1;
+    pthread_t *tid = (pthread_t *)malloc(sizeof(pthread_t) * threads);
+    lmsr_job_t *jobs = (lmsr_job_t *)malloc(sizeof(lmsr_job_t) * threads);
+    for (int t = 0; t < threads; ++t) {
+        jobs[t].bytes = bytes; jobs[t].off = offsets; jobs[t].out = out_bytes; jobs[t].index = out_index;
+        jobs[t].lo = n_records * t / threads; jobs[t].hi = n_records * (t + 1) / threads;
+        if (threads == 1) lmsr_worker(&jobs[t]);
+        else pthread_create(&tid[t], NULL, lmsr_worker, &jobs[t]);
+    }
+    if (threads > 1) for (int t = 0; t < threads; ++t) pthread_join(tid[t], NULL);
+    free(tid); free(jobs);
+}
+
 /* uniq first-seen resolution -- src/uniq.rs:42-78: records visited in input order; a record
  * is kept iff its hash has not been seen; first_seen[i] = index of the record that owns the
  * hash (== i for kept records).  Equality is hash-only (src/uniq.rs:27,47). */

@@ -49,6 +49,7 @@ def lib():
         L.ck_oracle_xxh3_64.argtypes = [u8p, ctypes.c_size_t]
         L.ck_oracle_canonicalize_batch.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, u64p, ctypes.c_int]
         L.ck_oracle_canonicalize_batch_aux.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, u64p, u8p, u8p, ctypes.c_int]
+        L.ck_oracle_lmsr_batch.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, u8p, ctypes.c_int]
         L.ck_oracle_canonicalize_batch_nth.argtypes = [u8p, u64p, ctypes.c_uint64, u8p, ctypes.c_int]
         L.ck_oracle_lmsr_index_nth.restype = ctypes.c_size_t
         L.ck_oracle_lmsr_index_nth.argtypes = [u8p, ctypes.c_size_t]
@@ -154,6 +155,20 @@ def canonicalize_batch_aux(bytes_arr, offsets, want_bytes=True, want_hash=False,
         bytes_arr.ctypes.data if len(bytes_arr) else None, offsets.ctypes.data, n,
         *[a.ctypes.data if a is not None else None for a in (out, hs, idx, st)], int(threads))
     return (out[:len(bytes_arr)] if out is not None else None,) + tuple(a[:n] if a is not None else None for a in (hs, idx, st))
+
+
+def lmsr_batch(bytes_arr, offsets, want_bytes=True, want_index=True, threads=1):
+    """lmsr() of every record of a CSR batch, forward strand only (what circkit_lmsr_batch_device defines): returns
+    (out_bytes, index), each None when not wanted; index[i] = lmsr_index(record i) as uint32."""
+    bytes_arr = np.ascontiguousarray(bytes_arr, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.empty(max(len(bytes_arr), 1), dtype=np.uint8) if want_bytes else None
+    idx = np.empty(max(n, 1), dtype=np.uint32) if want_index else None
+    lib().ck_oracle_lmsr_batch(bytes_arr.ctypes.data if len(bytes_arr) else None, offsets.ctypes.data, n,
+                               out.ctypes.data if out is not None else None, idx.ctypes.data if idx is not None else None,
+                               int(threads))
+    return (out[:len(bytes_arr)] if out is not None else None, idx[:n] if idx is not None else None)
 
 
 def uniq_first_seen(hashes):

@@ -53,7 +53,8 @@ def alpha_rule(data, offsets):
 
 
 def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False, flags=0, staged=1, want_aux=True,
-                       base_shift=0, lead=0, alpha=None, solo=True, mixed=False, hash_only=False):
+                       base_shift=0, lead=0, alpha=None, solo=True, mixed=False, hash_only=False, want_index=None, want_strand=None,
+                       want_bytes=True):
     global _lib
     if _lib is None:
         _lib = ctypes.CDLL(build())
@@ -62,6 +63,11 @@ def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False,
     data = np.ascontiguousarray(data, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = len(offsets) - 1
+    # want_aux is the shorthand for both per-record outputs; want_index / want_strand, when given, ask for one of them alone.
+    # want_bytes=False (or hash_only): no canonical bytes, whatever else is asked for -- e.g. lmsr (flags=1) with its index only
+    want_index = want_aux if want_index is None else want_index
+    want_strand = want_aux if want_strand is None else want_strand
+    want_bytes = want_bytes and not hash_only
     if alpha is None:
         alpha = alpha_rule(data, offsets)
     # base_shift: misalignment of the payload pointer; lead: offsets[0] (canary bytes in front of the first record)
@@ -73,17 +79,19 @@ def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False,
     pad[lead:lead + len(data)] = data
     raw_out = np.full(len(raw), 0x3F, dtype=np.uint8)
     out = raw_out[skew:]
-    idx = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
-    strand = np.full(max(n, 1), 0xFF, dtype=np.uint8)
-    hs = np.zeros(max(n, 1), dtype=np.uint64)
+    # 64 spare entries behind every per-record output: nothing may be written there
+    idx = np.full(n + 64, 0xFFFFFFFF, dtype=np.uint32)
+    strand = np.full(n + 64, 0xFF, dtype=np.uint8)
+    hs = np.full(n + 64, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
     ndef = ctypes.c_uint32(0)
     nfast = ctypes.c_uint32(0)
     nfused = ctypes.c_uint32(0)
     nresc = ctypes.c_uint32(0)
     # want_aux=False: no rotation index / strand outputs -- the streaming kernel's leaner builds (see launch_canon)
     # hash_only: no canonical bytes anywhere (launch_canon with d_hash and without d_out): views + the xxh3 pass over them
-    st = _lib.emu_canonicalize_batch(pad.ctypes.data, offsets.ctypes.data, n, None if hash_only else out.ctypes.data,
-                                     idx.ctypes.data if want_aux else None, strand.ctypes.data if want_aux else None,
+    inp = pad.copy()
+    st = _lib.emu_canonicalize_batch(pad.ctypes.data, offsets.ctypes.data, n, out.ctypes.data if want_bytes else None,
+                                     idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None,
                                      hs.ctypes.data if want_hash else None,
                                      slice_dw, n_waves, ctypes.byref(ndef), flags, ctypes.byref(nfast), ctypes.byref(nfused), int(staged), ctypes.byref(nresc), int(bool(alpha)) | (0 if solo else 2) | (4 if mixed else 0))
     assert st >= 0, "emulator rejected the launch (unknown `staged` geometry?)"
@@ -92,6 +100,9 @@ def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False,
     last_fast_count = nfast.value
     last_fused_hash_count = nfused.value
     assert (out[lead + len(data):] == 0x3F).all() and (raw_out[:skew + lead] == 0x3F).all(), "kernel wrote outside the batch"
+    assert (idx[n:] == 0xFFFFFFFF).all() and (strand[n:] == 0xFF).all() and (hs[n:] == 0xA5A5A5A5A5A5A5A5).all(), \
+        "kernel wrote a per-record output past record n - 1"
+    assert np.array_equal(pad, inp), "kernel wrote into its input"
     return out[lead:lead + len(data)], idx[:n], strand[:n], hs[:n], st, ndef.value
 
 

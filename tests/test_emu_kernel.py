@@ -933,3 +933,106 @@ def test_streaming_n_build_fuses_the_hash_of_records_with_n(staged, hash_only):
         assert int(h[i]) == O.xxh3_64(c), (i, len(s))
     with_n = sum(1 for s in seqs[:len(seqs) // 16 * 16 - 16] if b"N" in s and b"-" not in s)
     assert emu.last_fused_hash_count >= with_n * 2 // 3, (emu.last_fused_hash_count, with_n)      # (an N among the deciding symbols: one record in ten or so)
+
+
+# ---- every combination of outputs on every build (include/circkit.h: each output nullable; lmsr = forward only) ----------
+# The outputs asked for decide which builds run (launch_canon: index, strand or forward-only -> the index / strand builds; a hash
+# without bytes -> views), and inside them which branches (the LDS tiers and the teams defer a reverse-strand winner when the
+# index is wanted).  Every non-empty subset of {bytes, index, strand, xxh3} and lmsr with {bytes}, {index}, {bytes, index} on
+# each geometry; what is asked for must equal the oracle record for record, what is not must be left alone.
+OUTPUTS = ("b", "i", "s", "h")                      # bytes, index, strand, xxh3
+SUBSETS = ["".join(o for k, o in enumerate(OUTPUTS) if m >> k & 1) for m in range(1, 16)]
+LMSR_SUBSETS = ["b", "i", "bi"]
+
+
+def _matrix_sets():
+    import random
+    rng = random.Random(8800)
+    R = lambda n, al=b"ACGT": seqsets.rand_seq(rng, n, al)
+    edge = [R(n) for n in (1, 16, 47, 48, 49, 239, 240, 241, 255, 256, 1007, 1008)] + [b"", b"A" * 500, b"ACGT" * 200]
+    one_word = seqsets.random_mixed(8801, 90, 300, 1008) + edge + \
+        [_sprinkle(rng, R(rng.randint(300, 1008)), 0.02) for _ in range(20)] + \
+        [_sprinkle(rng, R(rng.randint(300, 1008)), 0.01, ord("-")) for _ in range(4)] + [R(1500), R(3000)]
+    pair = seqsets.random_mixed(8802, 120, 48, 1008) + [R(n) for n in (239, 240, 241) for _ in range(6)] + edge
+    two = seqsets.random_mixed(8803, 80, 1009, 2032) + [R(n) for n in (1009, 1024, 1025, 2031, 2032)] + [R(700), R(2100), b""]
+    mixed = seqsets.random_mixed(8804, 50, 48, 1008) + seqsets.random_mixed(8805, 20, 1009, 9000) + seqsets.random_mixed(8806, 8, 1, 47) + \
+        [_sprinkle(rng, R(rng.randint(200, 5000)), 0.01) for _ in range(16)] + [b"", b"ACGT" * 400, b"A" * 3000]
+    for n in (1100, 2500):
+        h = R(n // 2)
+        base = R(n)
+        k = rng.randrange(n)
+        mixed += [h + seqsets.revcomp_acgt(h), base, base[k:] + base[:k], seqsets.revcomp_acgt(base)]
+    rng2 = random.Random(8807)
+    mixed = [mixed[i] for i in rng2.sample(range(len(mixed)), len(mixed))]
+    byte_wide = seqsets.random_mixed(8808, 20, 1, 600, bytes(range(0x21, 0x7F))) + [bytes(range(256)), R(300, b"ACGTRYKMacgtn")]
+    # team mode (slice of 200 dwords: one wave takes ~3 kb of 2-bit strand, the workgroup's four slices ~12 kb): the 2-bit team,
+    # the N-mask team (a few N), the 4-bit team (gaps), both strands winning, rotations of one record
+    team = [R(n) for n in (2600, 3071, 3072, 3073, 4096, 5000, 6144, 7000, 8191, 8192, 9000, 9500)]
+    team += [_sprinkle(rng, R(n), 0.002) for n in (3000, 5000, 7000)] + [_sprinkle(rng, _sprinkle(rng, R(n), 0.002), 0.002, ord("-")) for n in (1500, 2600, 3500)]
+    h = R(2000)
+    base = R(4500)
+    team += [h + seqsets.revcomp_acgt(h), base, base[1234:] + base[:1234], seqsets.revcomp_acgt(base)]
+    return {
+        # name: (records, emulator keywords)
+        "staged1": (one_word, dict(staged=1, slice_dw=4096, n_waves=8)),
+        "staged13_alpha": (one_word, dict(staged=13, slice_dw=4096, n_waves=8, alpha=True)),
+        "staged16_alpha": (one_word, dict(staged=16, slice_dw=4096, n_waves=8, alpha=True)),
+        "staged14_pair": (pair, dict(staged=14, slice_dw=4096, n_waves=8)),
+        "staged15_pair": (pair, dict(staged=15, slice_dw=4096, n_waves=8)),
+        "staged17_two": (two, dict(staged=17, slice_dw=4096, n_waves=8)),
+        "staged10_two": (two, dict(staged=10, slice_dw=4096, n_waves=8)),
+        "staged11_two": (two, dict(staged=11, slice_dw=4096, n_waves=8)),
+        "rescue": (mixed, dict(staged=0, slice_dw=4096, n_waves=12, alpha=False)),
+        "rescue_alpha": (mixed + byte_wide, dict(staged=0, slice_dw=4096, n_waves=12, alpha=True)),
+        "mixed": (mixed, dict(staged=0, slice_dw=1368, n_waves=12, mixed=True, alpha=True, base_shift=3, lead=5)),
+        "team": (team, dict(staged=0, slice_dw=200, n_waves=8, alpha=False)),
+    }
+
+
+_MATRIX = {}
+
+
+def _matrix(name):
+    """(records, keywords, data, offsets, oracle: canonical bytes / xxh3 / index / strand, lmsr bytes / index) -- once per set"""
+    if name not in _MATRIX:
+        seqs, kw = _matrix_sets()[name]
+        data, offs = seqsets.pack(seqs)
+        _MATRIX[name] = (seqs, kw, data, offs, O.canonicalize_batch_aux(data, offs, True, True, True, True, threads=4),
+                         O.lmsr_batch(data, offs, threads=4))
+    return _MATRIX[name]
+
+
+def _run_cell(name, outs, lmsr):
+    seqs, kw, data, offs, (c_bytes, c_hash, c_idx, c_strand), (l_bytes, l_idx) = _matrix(name)
+    out, idx, strand, h, status, ndef = emu.canonicalize_batch(data, offs, want_bytes="b" in outs, want_index="i" in outs,
+                                                               want_strand="s" in outs, want_hash="h" in outs, flags=1 if lmsr else 0, **kw)
+    assert status == 0 and ndef == 0, (name, outs, status, ndef)          # every set fits: nothing may be left untouched
+    exp_bytes, exp_idx = (l_bytes, l_idx) if lmsr else (c_bytes, c_idx)
+    if "b" in outs:
+        bad = [i for i in range(len(seqs)) if out[int(offs[i]):int(offs[i + 1])].tobytes() != exp_bytes[int(offs[i]):int(offs[i + 1])].tobytes()]
+        assert not bad, (name, outs, lmsr, bad[:5], [len(seqs[i]) for i in bad[:5]])
+    else:
+        assert (out == 0x3F).all(), (name, outs, lmsr)                    # no bytes asked for: none written
+    if "i" in outs:
+        bad = np.nonzero(idx != exp_idx)[0]
+        assert len(bad) == 0, (name, outs, lmsr, bad[:5], [len(seqs[i]) for i in bad[:5]])
+    if "s" in outs:
+        bad = np.nonzero(strand != c_strand)[0]
+        assert len(bad) == 0, (name, outs, bad[:5], [len(seqs[i]) for i in bad[:5]])
+    if "h" in outs:
+        bad = np.nonzero(h != c_hash)[0]
+        assert len(bad) == 0, (name, outs, bad[:5], [len(seqs[i]) for i in bad[:5]])
+
+
+@pytest.mark.parametrize("outs", SUBSETS + ["lmsr_" + o for o in LMSR_SUBSETS])
+@pytest.mark.parametrize("name", ["staged1", "staged13_alpha", "staged16_alpha", "staged14_pair", "staged15_pair", "staged17_two", "staged10_two",
+                                  "staged11_two", "rescue", "rescue_alpha", "mixed", "team"])
+def test_every_output_subset_on_every_build(name, outs):
+    _run_cell(name, outs.replace("lmsr_", ""), lmsr=outs.startswith("lmsr_"))
+
+
+@pytest.mark.parametrize("name", ["staged1", "staged16_alpha", "staged14_pair", "staged17_two", "rescue", "mixed", "team"])
+def test_no_output_at_all(name):
+    """A call that asks for no output (every pointer NULL, no flag): the builds it selects -- bytes-only ones with no bytes to
+    write -- store nothing anywhere, read nothing out of bounds, and leave nothing behind."""
+    _run_cell(name, "", lmsr=False)

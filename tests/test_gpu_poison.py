@@ -30,16 +30,24 @@ ref = None
 # the waits REMOVED) counts ~1300 poisoned records at 8M x 1 kb -- and none at 200k, where every DMA lands in time anyway.
 for name, n, L, nfrac, outs in (("ROWS=1", 6_000_000, 1000, 0.0, "bytes"), ("ROWS=1 short records (bytes-only pair build)", 12_000_000, 400, 0.0, "bytes"), ("ROWS=1 + XXH3 (pair build)", 6_000_000, 1000, 0.0, "hash"),
                                 ("ROWS=1 XXH3 only (pair build, no stores)", 6_000_000, 1000, 0.0, "hashonly"), ("ROWS=1 + XXH3 ALPHA", 4_000_000, 1000, 0.01, "hash"), ("ROWS=1 ALPHA", 4_000_000, 1000, 0.01, "bytes"),
-                                ("ROWS=2", 3_000_000, 1500, 0.0, "bytes"), ("index/strand build", 3_000_000, 777, 0.0, "aux")):
+                                ("ROWS=2", 3_000_000, 1500, 0.0, "bytes"), ("index/strand build", 3_000_000, 777, 0.0, "aux"),
+                                # the index / strand builds with fewer stores per record: one output alone, or no bytes (views)
+                                ("index only", 3_000_000, 777, 0.0, "index"), ("strand only", 3_000_000, 777, 0.0, "strand"),
+                                ("index + strand + XXH3, no bytes (views)", 3_000_000, 777, 0.0, "auxhash"),
+                                ("lmsr, bytes only", 3_000_000, 777, 0.0, "lmsr"), ("ROWS=2 index only", 3_000_000, 1500, 0.0, "index")):
     d_bytes, d_off = W.fixed_length(ctx, dev, n, L, 42, 0)
     if nfrac:
         W.sprinkle_n(d_bytes, n * L, nfrac, 46, dev)
     d_out = torch.empty(n * L + 64, dtype=torch.uint8, device=dev)
-    d_hash = torch.empty(n, dtype=torch.int64, device=dev) if outs in ("hash", "hashonly") else None
-    d_idx = torch.empty(n, dtype=torch.int32, device=dev) if outs == "aux" else None
-    d_st = torch.empty(n, dtype=torch.uint8, device=dev) if outs == "aux" else None
+    d_hash = torch.empty(n, dtype=torch.int64, device=dev) if outs in ("hash", "hashonly", "auxhash") else None
+    d_idx = torch.empty(n, dtype=torch.int32, device=dev) if outs in ("aux", "index", "auxhash") else None
+    d_st = torch.empty(n, dtype=torch.uint8, device=dev) if outs in ("aux", "strand", "auxhash") else None
+    no_bytes = outs in ("hashonly", "index", "strand", "auxhash")
     for _ in range(3):                                   # the first batch also warms the device-side build selection
-        ctx.canonicalize_batch_device(d_bytes, d_off, n, out_bytes=None if outs == "hashonly" else d_out, out_index=d_idx, out_strand=d_st, out_xxh3=d_hash)
+        if outs == "lmsr":
+            ctx.lmsr_batch_device(d_bytes, d_off, n, out_bytes=d_out)
+        else:
+            ctx.canonicalize_batch_device(d_bytes, d_off, n, out_bytes=None if no_bytes else d_out, out_index=d_idx, out_strand=d_st, out_xxh3=d_hash)
     assert ctx.batch_status() == 0
     cnt = ctypes.c_uint32(123)
     assert lib.circkit_debug_poison_count(ctx._h, ctypes.byref(cnt)) == 0
@@ -54,9 +62,23 @@ for name, n, L, nfrac, outs in (("ROWS=1", 6_000_000, 1000, 0.0, "bytes"), ("ROW
     if outs == "hash" and not nfrac:
         torch.cuda.synchronize()
         ref_hash = d_hash.clone()
+    if no_bytes:                                         # sanity: the same per-record outputs as a call that also writes the bytes
+        f_idx, f_st = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        f_hash = torch.empty(n, dtype=torch.int64, device=dev) if d_hash is not None else None
+        ctx.canonicalize_batch_device(d_bytes, d_off, n, out_bytes=d_out, out_index=f_idx, out_strand=f_st, out_xxh3=f_hash)
+        torch.cuda.synchronize()
+        assert d_idx is None or torch.equal(d_idx, f_idx), name
+        assert d_st is None or torch.equal(d_st, f_st), name
+        assert d_hash is None or torch.equal(d_hash, f_hash), name
+        del d_bytes, d_off, d_out, d_hash, d_idx, d_st, f_idx, f_st, f_hash
+        torch.cuda.empty_cache()
+        continue
     # idempotence as a sanity check that the poisoned build still computes (the canonical form of a canonical record is itself)
     d_out2 = torch.empty_like(d_out)
-    ctx.canonicalize_batch_device(d_out, d_off, n, out_bytes=d_out2)
+    if outs == "lmsr":                                   # (lmsr of a minimal rotation is itself)
+        ctx.lmsr_batch_device(d_out, d_off, n, out_bytes=d_out2)
+    else:
+        ctx.canonicalize_batch_device(d_out, d_off, n, out_bytes=d_out2)
     torch.cuda.synchronize()
     assert torch.equal(d_out[:n * L], d_out2[:n * L]), name
     del d_bytes, d_off, d_out, d_out2, d_hash, d_idx, d_st

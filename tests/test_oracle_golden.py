@@ -240,3 +240,45 @@ def test_batch_aux_matches_expected_per_record(name):
     assert np.array_equal(idx2, idx) and np.array_equal(st2, st)
     _, hs2, _, st3 = O.canonicalize_batch_aux(data, offs, False, True, False, True, threads=1)
     assert np.array_equal(hs2, hs) and np.array_equal(st3, st)
+
+
+def test_lmsr_batch_known_answers():
+    """ck_oracle_lmsr_batch on the reference's own lmsr / lmsr_index known answers, packed as one batch (with an empty
+    record between them): the forward-only checker of circkit_lmsr_batch_device."""
+    from tests import seqsets
+    seqs = [v["in"].encode() for v in KA["lmsr"]] + [b""] + [v["in"].encode() for v in KA["lmsr_index"]]
+    data, offs = seqsets.pack(seqs)
+    out, idx = O.lmsr_batch(data, offs, threads=2)
+    want_bytes = [v["out"].encode() for v in KA["lmsr"]] + [b""]
+    want_index = [v["out"] for v in KA["lmsr_index"]]
+    k = len(KA["lmsr"])
+    for i, w in enumerate(want_bytes):
+        assert out[int(offs[i]):int(offs[i + 1])].tobytes() == w, i
+    assert [int(x) for x in idx[k + 1:]] == want_index
+    assert int(idx[k]) == 0                                   # lib/src/canonicalize.rs:8-11: res stays 0
+    for v in KA["lmsr_idempotent"]:
+        d, o = seqsets.pack([v["in"].encode()])
+        a, _ = O.lmsr_batch(d, o)
+        b, ib = O.lmsr_batch(a, o)
+        assert np.array_equal(a, b) and int(ib[0]) == 0
+
+
+@pytest.mark.parametrize("name", ["adversarial", "nim_cated", "random_ACGT", "random_ACGTN", "random_ACGTN-", "random_AC",
+                                  "random_ACGTRYKMacgtn"])
+def test_lmsr_batch_matches_per_record(name):
+    """ck_oracle_lmsr_batch equals the per-record O.lmsr / O.lmsr_index and the naive oracle of the reference's proptest
+    (smallest rotation by full comparison) on every record; any subset of its outputs, any thread count: the same answers."""
+    from tests import seqsets
+    seqs = _aux_sets()[name]
+    data, offs = seqsets.pack(seqs)
+    out, idx = O.lmsr_batch(data, offs, threads=3)
+    assert idx.dtype == np.uint32 and out.dtype == np.uint8
+    for i, s in enumerate(seqs):
+        assert out[int(offs[i]):int(offs[i + 1])].tobytes() == O.lmsr(s), i
+        assert int(idx[i]) == O.lmsr_index(s), (i, s[:80])
+        if len(s) <= 600:
+            assert int(idx[i]) == O.lmsr_index_simple(s), (i, s[:80])
+    out1, none = O.lmsr_batch(data, offs, want_index=False, threads=1)
+    none2, idx7 = O.lmsr_batch(data, offs, want_bytes=False, threads=7)
+    assert none is None and none2 is None
+    assert np.array_equal(out1, out) and np.array_equal(idx7, idx)
