@@ -66,8 +66,55 @@ SIGNATURES = {
     "circkit_fixed_offsets_device": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "circkit_bench_copy_device": (_i, [_vp, _vp, _vp, _u64, _u32]),
     "circkit_normalize": (_sz, [_vp, _sz, _vp, ctypes.POINTER(_i)]),
+    "circkit_orfs_batch_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64]),
+    "circkit_orfs_status": (_i, [_vp, ctypes.POINTER(_u64)]),
+    "circkit_orfs_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
+    "circkit_find_orfs": (_i, [_vp, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
+
+# circkit_orf / circkit_orf_params (include/circkit.h)
+ORF_NO_STOP = 0xFFFFFFFF
+ORF_DTYPE = np.dtype([("length", "<u8"), ("start", "<u4"), ("stop", "<u4"), ("wraps", "<u4"), ("strand", "<u4")])
+
+
+class OrfParams(ctypes.Structure):
+    _fields_ = [("start_codons", (ctypes.c_uint8 * 3) * 64), ("n_start_codons", _u32),
+                ("stop_codons", (ctypes.c_uint8 * 3) * 64), ("n_stop_codons", _u32),
+                ("min_length", _u64), ("min_ratio", ctypes.c_double), ("min_wraps", _u32), ("max_wraps", _u32),
+                ("require_stop", _u32), ("strands", _u32), ("mode", _u32)]
+
+
+STRANDS = {"forward": 1, "reverse": 2, "both": 3}
+
+
+def orf_params(start_codons=("ATG",), stop_codons=("TAA", "TAG", "TGA"), min_length=0, min_ratio=0.0, min_wraps=0, max_wraps=3,
+               require_stop=False, strands="both", mode="longest"):
+    """circkit_orf_params from Python values.  Codons are str/bytes; one whose length is not 3 never matches (the
+    reference compares &str) and is left out.  strands: "forward" | "reverse" | "both" or a bit mask; mode: "longest"
+    (per stop, the CLI) or "all" (find order)."""
+    p = OrfParams()
+    for field, codons in (("start", start_codons), ("stop", stop_codons)):
+        cs = [c.encode() if isinstance(c, str) else bytes(c) for c in codons]
+        cs = [c for c in cs if len(c) == 3]
+        if len(cs) > 64:
+            raise ValueError("at most 64 %s codons" % field)
+        arr = getattr(p, field + "_codons")
+        for k, c in enumerate(cs):
+            for j in range(3):
+                arr[k][j] = c[j]
+        setattr(p, "n_%s_codons" % field, len(cs))
+    p.min_length, p.min_ratio = int(min_length), float(min_ratio)
+    p.min_wraps, p.max_wraps, p.require_stop = int(min_wraps), int(max_wraps), int(bool(require_stop))
+    p.strands = STRANDS[strands] if isinstance(strands, str) else int(strands)
+    p.mode = {"longest": 0, "all": 1}[mode] if isinstance(mode, str) else int(mode)
+    return p
+
+
+def _orf_arrays(offsets, orfs):
+    return {"offsets": offsets, "start": orfs["start"].copy(), "stop": orfs["stop"].copy(), "length": orfs["length"].copy(),
+            "wraps": orfs["wraps"].copy(), "strand": orfs["strand"].copy()}
+
 
 _lib = None
 
@@ -262,6 +309,57 @@ class Context:
                 "strand": st[:n] if st is not None else None,
                 "xxh3": hs[:n] if hs is not None else None}
 
+    # -- circular ORFs ---------------------------------------------------------------------------
+    def orfs_batch_device(self, d_bytes, d_offsets, n_records, d_orf_offsets, d_orfs, capacity, params=None, **kw):
+        """Enqueues circkit_orfs_batch_device.  d_orfs: a device buffer of `capacity` 24-byte descriptors (ORF_DTYPE);
+        orfs_status() waits and returns the total."""
+        p = params if params is not None else orf_params(**kw)
+        self._check(self._lib.circkit_orfs_batch_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), ctypes.byref(p),
+                                                        _ptr(d_orf_offsets), _ptr(d_orfs), int(capacity)))
+
+    def orfs_status(self):
+        """Waits for the last orfs_batch_device; returns its total, raises CirckitError (OOM) beyond the capacity."""
+        t = _u64(0)
+        self._check(self._lib.circkit_orfs_status(self._h, ctypes.byref(t)))
+        return t.value
+
+    def orfs_batch(self, data, offsets, **params):
+        """ORFs of every record of a host CSR batch of normalized records (see orf_params for the keywords).  Returns numpy
+        arrays: offsets (n + 1; record i's ORFs are [offsets[i], offsets[i+1]), forward before reverse), start, stop
+        (ORF_NO_STOP = None), length, wraps, strand (0 forward, 1 reverse)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        p = orf_params(**params)
+        orf_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(n, 1) * 4
+        while True:
+            orfs = np.zeros(cap, dtype=ORF_DTYPE)
+            total = _u64(0)
+            rc = self._lib.circkit_orfs_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, ctypes.byref(p),
+                                              _ptr(orf_off), _ptr(orfs), cap, ctypes.byref(total))
+            if rc == -5 and total.value > cap:           # grow to the reported total and run again
+                cap = total.value
+                continue
+            self._check(rc)
+            return _orf_arrays(orf_off, orfs[:total.value])
+
+    def find_orfs(self, s):
+        """lib/src/orfs.rs:41 find_orfs: [(start, stop or None, wraps, length)] in the reference's order."""
+        s = bytes(s)
+        buf = ctypes.create_string_buffer(s, max(len(s), 1))
+        cap = max(len(s), 1)
+        while True:
+            out = np.zeros(cap, dtype=ORF_DTYPE)
+            cnt = _sz(0)
+            rc = self._lib.circkit_find_orfs(self._h, ctypes.addressof(buf), len(s), _ptr(out), cap, ctypes.byref(cnt))
+            if rc == -5 and cnt.value > cap:
+                cap = cnt.value
+                continue
+            self._check(rc)
+            return [(int(o["start"]), None if int(o["stop"]) == ORF_NO_STOP else int(o["stop"]), int(o["wraps"]), int(o["length"]))
+                    for o in out[:cnt.value]]
+
     # -- single record: the lib-crate API --------------------------------------------------------
     def _single(self, fn, s):
         s = bytes(s)
@@ -326,6 +424,10 @@ def canonicalize(s):
 
 def xxh3_64(s):
     return default_context().xxh3_64(s)
+
+
+def find_orfs(s):
+    return default_context().find_orfs(s)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

@@ -11,6 +11,7 @@
 // packs CSR batches (fasta_host.h) and writes text out.  There is no CPU compute path: without a usable GPU the
 // program fails like any other I/O error.  Compressed streams are piped through the system's gzip / bzip2 / xz /
 // zstd binaries.
+#include <ctype.h>
 #include <dlfcn.h>
 #include <errno.h>
 #include <math.h>
@@ -26,6 +27,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -50,6 +52,11 @@ struct Options {
     bool has_bases = false, has_percent = false;        // rotate
     long long bases = 0;
     double percent = 0.0;
+    // orfs (src/commands.rs:174-244)
+    uint64_t min_length = 75, min_wraps = 0, max_wraps = 3;
+    std::string start_codons = "ATG", stop_codons = "TAA,TAG,TGA", strand = "both";
+    bool include_stop = false, no_stop_required = false;
+    double min_ratio = 0.0;
 };
 
 [[noreturn]] void die(const std::string& msg)
@@ -67,7 +74,10 @@ void usage(FILE* f)
             "    circkit uniq [INPUT] [-o <OUTPUT>] [-c|--canonicalize] [--table <TABLE>] [-t <THREADS>]\n"
             "    circkit rotate [INPUT] [-o <OUTPUT>] (-b|--bases <N> | -p|--percent <FRACTION>)\n"
             "    circkit cat [INPUT] [-o <OUTPUT>]\n"
-            "    circkit decat [INPUT] [-o <OUTPUT>]\n\n"
+            "    circkit decat [INPUT] [-o <OUTPUT>]\n"
+            "    circkit orfs [INPUT] [-o <OUTPUT>] [-m|--min-length <N>] [--start-codons <LIST>] [--stop-codons <LIST>]\n"
+            "                 [--include-stop] [--no-stop-required] [--min-wraps <N>] [--max-wraps <N>]\n"
+            "                 [--strand forward|reverse|both] [--min-ratio <R>] [--table <TABLE>] [-t <THREADS>]\n\n"
             "    INPUT   FASTA file, may be gzip, bzip, xz, or zstd compressed [default: stdin]\n"
             "    -o      output FASTA path; .gz/.bz2/.xz/.zst compress [default: stdout]\n"
             "    -c      uniq: output canonicalized sequences (aliases --norm --canon)\n"
@@ -76,7 +86,10 @@ void usage(FILE* f)
             "    --device <N>  GPU index [default: 0]\n"
             "    -b      rotate: bases to rotate by (positive: to the right, negative: to the left)\n"
             "    -p      rotate: fraction of the sequence length to rotate by, e.g. 0.5\n"
-            "  canonicalize and uniq run on the GPU; rotate, cat and decat are byte copies done on the host.\n");
+            "    orfs    circular ORFs on both strands; --table writes orf_id,seq_id,start,stop,length,wraps,ratio\n"
+            "            [defaults: -m 75, --start-codons ATG, --stop-codons TAA,TAG,TGA, --min-wraps 0, --max-wraps 3,\n"
+            "             --strand both, --min-ratio 0]\n"
+            "  canonicalize, uniq and orfs run on the GPU; rotate, cat and decat are byte copies done on the host.\n");
 }
 
 // clap's accepted forms for the arms this binary provides (src/commands.rs:6-14,93-180; clap 3 derive defaults): long options
@@ -114,11 +127,20 @@ Options parse_args(int argc, char** argv)
     o.cmd = argv[i++];
     if (o.cmd == "-h" || o.cmd == "--help" || o.cmd == "help") { usage(stdout); exit(0); }
     if (o.cmd == "-V" || o.cmd == "--version") { printf("circkit 0.1.0 (MI355X build)\n"); exit(0); }
-    if (o.cmd != "canonicalize" && o.cmd != "uniq" && o.cmd != "rotate" && o.cmd != "cat" && o.cmd != "decat") {
-        fprintf(stderr, "error: unrecognized subcommand '%s' (this build provides canonicalize, uniq, rotate, cat, decat)\n", o.cmd.c_str());
+    if (o.cmd != "canonicalize" && o.cmd != "uniq" && o.cmd != "rotate" && o.cmd != "cat" && o.cmd != "decat" && o.cmd != "orfs") {
+        fprintf(stderr, "error: unrecognized subcommand '%s' (this build provides canonicalize, uniq, rotate, cat, decat, orfs)\n", o.cmd.c_str());
         exit(2);
     }
-    const bool gpu_cmd = o.cmd == "canonicalize" || o.cmd == "uniq", uniq = o.cmd == "uniq", rotate = o.cmd == "rotate";
+    const bool orfs = o.cmd == "orfs";
+    const bool gpu_cmd = o.cmd == "canonicalize" || o.cmd == "uniq" || orfs, uniq = o.cmd == "uniq", rotate = o.cmd == "rotate";
+    // clap's f64 parser (Rust's f64::from_str): decimal or exponent forms, inf / nan, no blanks, no hex
+    auto parse_f64 = [&](const std::string& v, const char* what) {
+        char* end = nullptr;
+        const double x = strtod(v.c_str(), &end);
+        if (v.empty() || *end || isspace((unsigned char)v[0]) || v.find_first_of("xX") != std::string::npos)
+            arg_error("invalid value '" + v + "' for '" + what + "'");
+        return x;
+    };
     // the valued options of this arm, by canonical long name
     auto set_value = [&](const std::string& name, const std::string& v) {
         if (name == "output") { o.output = v; o.has_output = true; }
@@ -126,6 +148,17 @@ Options parse_args(int argc, char** argv)
         else if (name == "device") o.device = (int)parse_int(v, "--device <N>", 0, 1 << 20);
         else if (name == "table") { o.table = v; o.has_table = true; }
         else if (name == "bases") { o.bases = parse_int(v, "--bases <BASES>", LLONG_MIN, LLONG_MAX); o.has_bases = true; }      // negative values allowed (src/commands.rs:164)
+        else if (name == "min-length") o.min_length = (uint64_t)parse_int(v, "--min-length <MIN_LENGTH>", 0, LLONG_MAX);
+        else if (name == "min-wraps") o.min_wraps = (uint64_t)parse_int(v, "--min-wraps <MIN_WRAPS>", 0, LLONG_MAX);
+        else if (name == "max-wraps") o.max_wraps = (uint64_t)parse_int(v, "--max-wraps <MAX_WRAPS>", 0, LLONG_MAX);
+        else if (name == "start-codons") o.start_codons = v;
+        else if (name == "stop-codons") o.stop_codons = v;
+        else if (name == "min-ratio") o.min_ratio = parse_f64(v, "--min-ratio <MIN_RATIO>");
+        else if (name == "strand") {
+            if (v != "forward" && v != "reverse" && v != "both")
+                arg_error("\"" + v + "\" isn't a valid value for '--strand <STRAND>'\n\t[possible values: forward, reverse, both]");
+            o.strand = v;
+        }
         else {
             char* end = nullptr;
             o.percent = strtod(v.c_str(), &end);
@@ -134,13 +167,16 @@ Options parse_args(int argc, char** argv)
         }
     };
     auto long_takes_value = [&](const std::string& n) {
-        return n == "output" || (gpu_cmd && (n == "threads" || n == "device")) || (uniq && n == "table") || (rotate && (n == "bases" || n == "percent"));
+        return n == "output" || (gpu_cmd && (n == "threads" || n == "device")) || ((uniq || orfs) && n == "table") || (rotate && (n == "bases" || n == "percent")) ||
+               (orfs && (n == "min-length" || n == "start-codons" || n == "stop-codons" || n == "min-wraps" || n == "max-wraps" || n == "strand" ||
+                         n == "min-ratio"));
     };
     auto short_name = [&](char ch) -> const char* {             // valued shorts
         if (ch == 'o') return "output";
         if (gpu_cmd && ch == 't') return "threads";
         if (rotate && ch == 'b') return "bases";
         if (rotate && ch == 'p') return "percent";
+        if (orfs && ch == 'm') return "min-length";
         return nullptr;
     };
     auto next_value = [&](const std::string& shown) -> std::string {
@@ -162,6 +198,8 @@ Options parse_args(int argc, char** argv)
             if (long_takes_value(name)) set_value(name, eq == std::string::npos ? next_value(a) : a.substr(eq + 1));
             else if (eq != std::string::npos) arg_error("unexpected value '" + a.substr(eq + 1) + "' for '--" + name + "' found; no more were expected");
             else if (uniq && (name == "canonicalize" || name == "norm" || name == "canon")) o.canonicalize = true;
+            else if (orfs && name == "include-stop") o.include_stop = true;
+            else if (orfs && name == "no-stop-required") o.no_stop_required = true;
             else if (name == "verbose" || name == "quiet") {}
             else if (name == "help") { usage(stdout); exit(0); }
             else if (name == "version") { printf("circkit 0.1.0 (MI355X build)\n"); exit(0); }
@@ -640,6 +678,245 @@ int run_host_edit(const Options& opt, Input& in, Output& out)
     return 0;
 }
 
+// An f64 as the csv crate writes it (ryu's format): the shortest digits that read back as the same double, `1.0`,
+// `0.5`, `0.00012`, `1e-7`, `1.5e-6` (src/orfs.rs:150,178 `ratio`).
+std::string ryu_f64(double x)
+{
+    char buf[40];
+    int p = 1;
+    for (; p < 17; ++p) { snprintf(buf, sizeof buf, "%.*e", p - 1, x); if (strtod(buf, nullptr) == x) break; }
+    snprintf(buf, sizeof buf, "%.*e", p - 1, x);
+    std::string digits;
+    const char* q = buf;
+    for (; *q && *q != 'e'; ++q) if (isdigit((unsigned char)*q)) digits += *q;
+    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+    const int e10 = atoi(q + 1);                       // x = d.ddd * 10^e10
+    const int len = (int)digits.size(), kk = e10 + 1;  // position of the decimal point
+    std::string r;
+    if (kk >= len && kk <= 16) { r = digits + std::string(kk - len, '0') + ".0"; }
+    else if (kk > 0 && kk <= 16) { r = digits.substr(0, kk) + "." + digits.substr(kk); }
+    else if (kk > -5 && kk <= 0) { r = "0." + std::string(-kk, '0') + digits; }
+    else {
+        r = digits.substr(0, 1);
+        if (len > 1) r += "." + digits.substr(1);
+        r += "e" + std::to_string(kk - 1);
+    }
+    return r;
+}
+
+// orfs (src/orfs.rs:25-192): the reader and parser of the streaming path (chunks cut at record starts, seq_io record
+// semantics, normalize), one circkit_orfs_batch per chunk on the GPU (the worker closure: codon indices, find, filter,
+// longest, both strands), then the writer closure on the host: `>{head}_ORF{start}` cut cyclically from full_seq(), `_RC_ORF`
+// from revcomp(normalized), in record order, forward before reverse, and the --table rows.
+int run_orfs(const Options& opt, Input& in, Output& out)
+{
+    circkit_orf_params prm;
+    memset(&prm, 0, sizeof prm);
+    // the reference splits the lists at ',' and compares 3-byte windows with `contains`: only 3-byte codons can match
+    auto codons = [&](const std::string& list, uint8_t (*dst)[3], uint32_t* n) {
+        std::vector<std::string> seen;
+        size_t a = 0;
+        for (;;) {
+            const size_t b = list.find(',', a);
+            const std::string c = list.substr(a, b == std::string::npos ? std::string::npos : b - a);
+            if (c.size() == 3 && std::find(seen.begin(), seen.end(), c) == seen.end()) {
+                if (seen.size() == CIRCKIT_ORF_MAX_CODONS) die("more than 64 distinct codons in a codon list");
+                memcpy(dst[seen.size()], c.data(), 3);
+                seen.push_back(c);
+            }
+            if (b == std::string::npos) break;
+            a = b + 1;
+        }
+        *n = (uint32_t)seen.size();
+    };
+    codons(opt.start_codons, prm.start_codons, &prm.n_start_codons);
+    codons(opt.stop_codons, prm.stop_codons, &prm.n_stop_codons);
+    prm.min_length = opt.min_length;
+    prm.min_ratio = opt.min_ratio;
+    prm.min_wraps = opt.min_wraps > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)opt.min_wraps;   // (wraps never exceed 3)
+    prm.max_wraps = opt.max_wraps > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)opt.max_wraps;
+    prm.require_stop = opt.no_stop_required ? 0 : 1;
+    prm.strands = opt.strand == "forward" ? 1 : 3;     // --strand reverse: the forward list is computed and written too (src/orfs.rs:79-103)
+    prm.mode = 0;
+    FILE* table = nullptr;
+    char delim = ',';
+    if (opt.has_table) {
+        table = fopen(opt.table.c_str(), "wb");
+        if (!table) die("Could not create output table.");                                 // src/utils.rs:83
+        if (opt.table.size() >= 4 && opt.table.compare(opt.table.size() - 4, 4, ".tsv") == 0) delim = '\t';   // src/utils.rs:77-80
+    }
+    circkit_ctx* ctx = nullptr;
+    check(ctx, circkit_ctx_create(opt.device, &ctx));
+    const size_t cut_bytes = 3 - (opt.include_stop ? 3 : 0);
+    bool table_header = false;
+    std::vector<uint64_t> orf_off;
+    std::vector<circkit_orf> orfs(1 << 16);
+    std::vector<uint8_t> own, carry;
+    std::string full, rc, line, row;
+    const uint8_t* comp = nullptr;
+    uint8_t comp_tab[256];
+    {                                                  // bio 1.3.1 alphabets::dna complement
+        for (int v = 0; v < 256; ++v) comp_tab[v] = (uint8_t)v;
+        const char *a = "AGCTYRWSKMDVHBN", *b = "TCGARYWSMKHBDVN";
+        for (int k = 0; a[k]; ++k) { comp_tab[(uint8_t)a[k]] = (uint8_t)b[k]; comp_tab[(uint8_t)a[k] + 32] = (uint8_t)(b[k] + 32); }
+        comp = comp_tab;
+    }
+    auto last_record_start = [](const uint8_t* buf, size_t len) -> size_t {
+        size_t k = len;
+        while (k > 1) {
+            const void* g = memrchr(buf + 1, '>', k - 1);
+            if (!g) return 0;
+            const size_t gi = (const uint8_t*)g - buf;
+            if (buf[gi - 1] == '\n') return gi;
+            k = gi;
+        }
+        return 0;
+    };
+    size_t map_pos = 0;
+    bool eof = false, first = true;
+    ckhost::Batch b;
+    while (true) {
+        // ---- read: a chunk of whole records ----
+        const uint8_t* text;
+        size_t len;
+        if (in.map) {
+            if (map_pos >= in.map_len) break;
+            size_t want = Pipeline::CHUNK, cut = 0;
+            for (;;) {
+                if (map_pos + want >= in.map_len) { cut = in.map_len - map_pos; break; }
+                cut = last_record_start(in.map + map_pos, want);
+                if (cut) break;
+                want *= 2;
+            }
+            text = in.map + map_pos; len = cut; map_pos += cut;
+        } else {
+            if (eof && carry.empty()) break;
+            size_t have = carry.size();
+            if (own.size() < have + Pipeline::CHUNK) own.resize(have + Pipeline::CHUNK);
+            memcpy(own.data(), carry.data(), have);
+            carry.clear();
+            size_t cut = 0;
+            for (;;) {
+                while (!eof && have < own.size()) {
+                    const size_t got = in_read(in, own.data() + have, own.size() - have);
+                    if (got == 0) { if (ferror(in.f)) die("failed to read the input"); eof = true; }
+                    have += got;
+                }
+                if (eof) { cut = have; break; }
+                cut = last_record_start(own.data(), have);
+                if (cut) break;
+                own.resize(own.size() * 2);
+            }
+            carry.assign(own.begin() + cut, own.begin() + have);
+            text = own.data(); len = cut;
+            if (len == 0) { if (eof && carry.empty()) break; continue; }
+        }
+        // ---- parse + normalize ----
+        b.clear();
+        std::string err;
+        size_t used = 0;
+        if (!ckhost::parse_chunk(text, len, first, true, b, &used, err)) die(err);
+        first = false;
+        const uint64_t n = b.n();
+        if (n == 0) continue;
+        for (uint64_t i = 0; i < n; ++i)
+            if (b.offsets[i + 1] - b.offsets[i] < 2) {         // `seq.len() - 2` underflows in the reference: a panic
+                fflush(out.f);
+                fprintf(stderr, "thread panicked: attempt to subtract with overflow (a record of fewer than 2 symbols)\n");
+                _exit(101);
+            }
+        // ---- the worker closure, for the whole chunk, on the GPU ----
+        orf_off.resize(n + 1);
+        uint64_t total = 0;
+        int rc_ = circkit_orfs_batch(ctx, b.bytes.data(), b.offsets.data(), n, &prm, orf_off.data(), orfs.data(), orfs.size(), &total);
+        if (rc_ == CIRCKIT_ERR_OOM && total > orfs.size()) {
+            orfs.resize(total);
+            rc_ = circkit_orfs_batch(ctx, b.bytes.data(), b.offsets.data(), n, &prm, orf_off.data(), orfs.data(), orfs.size(), &total);
+        }
+        check(ctx, rc_);
+        // ---- the writer closure ----
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t o0 = orf_off[i], o1 = orf_off[i + 1];
+            if (o0 == o1) continue;
+            const uint8_t* hp = text + b.head[i].off;
+            const size_t hl = b.head[i].len;
+            full.clear();                                  // full_seq(): the sequence lines without their terminators
+            {
+                const uint8_t* p = text + b.raw[i].off;
+                const size_t rn = b.raw[i].len;
+                for (size_t k = 0; k < rn;) {
+                    const uint8_t* nl = (const uint8_t*)memchr(p + k, '\n', rn - k);
+                    size_t e = nl ? (size_t)(nl - p) : rn;
+                    const size_t next = nl ? e + 1 : rn;
+                    if (e > k && p[e - 1] == '\r') --e;
+                    full.append((const char*)p + k, e - k);
+                    k = next;
+                }
+            }
+            const uint8_t* norm = b.bytes.data() + b.offsets[i];
+            const uint64_t L = b.offsets[i + 1] - b.offsets[i];
+            rc.resize(L);
+            for (uint64_t k = 0; k < L; ++k) rc[k] = (char)comp[norm[L - 1 - k]];
+            for (uint64_t k = o0; k < o1; ++k) {
+                const circkit_orf& f = orfs[k];
+                const std::string& src = f.strand == 0 ? full : rc;
+                const char* tag = f.strand == 0 ? "_ORF" : "_RC_ORF";
+                const uint64_t take = f.length - cut_bytes;
+                line.assign(">");
+                line.append((const char*)hp, hl);
+                line += tag;
+                line += std::to_string(f.start);
+                line += '\n';
+                if (!src.empty()) {
+                    uint64_t pos = f.start % src.size(), left = take;
+                    while (left) {
+                        const uint64_t m = std::min<uint64_t>(left, src.size() - pos);
+                        line.append(src, pos, m);
+                        left -= m; pos = 0;
+                    }
+                }
+                line += '\n';
+                if (fwrite(line.data(), 1, line.size(), out.f) != line.size()) die("failed to write output");
+                if (table) {
+                    if (!table_header) {
+                        const char* cols[] = { "orf_id", "seq_id", "start", "stop", "length", "wraps", "ratio" };
+                        row.clear();
+                        for (int c = 0; c < 7; ++c) { if (c) row += delim; row += cols[c]; }
+                        row += '\n';
+                        fwrite(row.data(), 1, row.size(), table);
+                        table_header = true;
+                    }
+                    const uint64_t t_start = f.strand == 0 ? f.start : L - 1 - f.start;      // src/orfs.rs:171-175
+                    row.clear();
+                    std::string id((const char*)hp, hl);
+                    id += tag;
+                    id += std::to_string(f.start);
+                    ckhost::csv_field(row, (const uint8_t*)id.data(), id.size(), delim);
+                    row += delim;
+                    if (hl) ckhost::csv_field(row, hp, hl, delim);
+                    row += delim;
+                    row += std::to_string(t_start);
+                    row += delim;
+                    if (f.stop != CIRCKIT_ORF_NO_STOP) row += std::to_string(f.strand == 0 ? (uint64_t)f.stop : L - 1 - f.stop);
+                    row += delim;
+                    row += std::to_string(f.length - cut_bytes);
+                    row += delim;
+                    row += std::to_string(f.wraps);
+                    row += delim;
+                    row += ryu_f64((double)f.length / (double)full.size());
+                    row += '\n';
+                    if (fwrite(row.data(), 1, row.size(), table) != row.size()) die("failed to write to table");
+                }
+            }
+        }
+    }
+    close_output(out);
+    if (table && fclose(table) != 0) die("failed to write to table");
+    close_input(in);
+    circkit_ctx_destroy(ctx);
+    return 0;
+}
+
 // The reference's default is num_cpus::get() (src/commands.rs:120-123): the CPUs this process may run on, and under a
 // cgroup CPU quota no more than the quota allows -- a container that shows 256 CPUs but grants 16 runs 64 threads slower
 // than 16 (measured on the GPU boxes: 2.5-3.2 against 3.8 M records/s).
@@ -719,6 +996,7 @@ int main(int argc, char** argv)
     Input in = open_input(opt);
     Output out = open_output(opt);
     if (opt.cmd == "rotate" || opt.cmd == "cat" || opt.cmd == "decat") return run_host_edit(opt, in, out);
+    if (opt.cmd == "orfs") return run_orfs(opt, in, out);
     FILE* table = nullptr;
     char delim = ',';
     if (opt.has_table) {

@@ -1253,7 +1253,16 @@ struct circkit_ctx {
     uint32_t mode_seen = 0;                   // launch_canon: the mode word as the previous device batch's launch read it (MODE_GUESS)
     bool uniq_local = false;                  // the table holds circkit_uniq_resolve_device's split local values
     bool uniq_lost = false;                   // a rehash failed half-way: the stream's earlier batches are gone -- every uniq call fails until circkit_uniq_reset
+
+    void* orfs = nullptr;                     // circkit_orfs.hip's buffers, freed by the function it registers with them
+    void (*orfs_release)(void*) = nullptr;
 };
+
+// circkit_orfs.hip's view of the ctx
+hipStream_t ck_ctx_stream(circkit_ctx* c) { return c->stream; }
+int ck_ctx_device(circkit_ctx* c) { return c->device; }
+int ck_ctx_fail(circkit_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+void** ck_ctx_orfs_slot(circkit_ctx* c, void (*release)(void*)) { c->orfs_release = release; return &c->orfs; }
 
 namespace {
 
@@ -1937,6 +1946,7 @@ int circkit_ctx_destroy(circkit_ctx* c)
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     if (c->h_mode) (void)hipHostFree((void*)c->h_mode);
     if (c->h_off) (void)hipHostFree((void*)c->h_off);
+    if (c->orfs_release) c->orfs_release(c->orfs);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return CIRCKIT_OK;

@@ -188,6 +188,73 @@ int circkit_uniq_status(circkit_ctx* ctx, uint32_t* n_overflowed);
 int circkit_uniq_first_seen(circkit_ctx* ctx, const uint64_t* hash, uint64_t n, uint64_t base_index,
                             uint64_t* first_seen);
 
+/* ---- circular ORFs (`circkit orfs`) --------------------------------------------------------------- */
+/* One ORF as lib/src/orfs.rs:6-15 defines it (pub struct Orf), plus the strand it was found on.  start and stop are
+ * positions on that strand (a reverse-strand ORF counts on revcomp(record), as the reference's RC list does);
+ * length includes the start and stop codons. */
+#define CIRCKIT_ORF_NO_STOP 0xFFFFFFFFu      /* stop: None */
+#define CIRCKIT_ORF_MAX_CODONS 64
+typedef struct circkit_orf {
+    uint64_t length;
+    uint32_t start;
+    uint32_t stop;                           /* CIRCKIT_ORF_NO_STOP = None */
+    uint32_t wraps;
+    uint32_t strand;                         /* 0 forward, 1 reverse */
+} circkit_orf;
+
+/* The worker closure's settings (src/commands.rs:174-244 flags, src/orfs.rs:25-104 uses):
+ *   start_codons / stop_codons  `--start-codons` / `--stop-codons` split at ','; a codon with a byte outside {ACGTN-}
+ *                               (lower case included) is dropped: it never matches a normalized record.  The
+ *                               batch entry points assume normalized records; on other bytes such a codon would
+ *                               match where the reference's byte comparison does, and this library's does not.
+ *                               Codons of another length never match either: leave them out.
+ *   min_length .. require_stop  the retain() filter of src/orfs.rs:68-74: length - 3 >= min_length, a stop unless
+ *                               !require_stop (`--no-stop-required`), min_wraps <= wraps <= max_wraps,
+ *                               length / L >= min_ratio (an f64 division)
+ *   strands                     bit 0 forward, bit 1 reverse (`--strand reverse` in the CLI still asks for both:
+ *                               src/orfs.rs:79-103 always computes the forward list)
+ *   mode                        0 = longest per stop, in longest_orfs' order (lib/src/orfs.rs:301-315: length, then
+ *                               start % 3, then start, all descending); 1 = every ORF that passes the filter, in
+ *                               find_orfs_with_indices' order (frame-major, start ascending) */
+typedef struct circkit_orf_params {
+    uint8_t start_codons[CIRCKIT_ORF_MAX_CODONS][3];
+    uint32_t n_start_codons;
+    uint8_t stop_codons[CIRCKIT_ORF_MAX_CODONS][3];
+    uint32_t n_stop_codons;
+    uint64_t min_length;
+    double min_ratio;
+    uint32_t min_wraps;
+    uint32_t max_wraps;
+    uint32_t require_stop;
+    uint32_t strands;
+    uint32_t mode;
+} circkit_orf_params;
+
+/* Replaces, for a whole batch of normalized records, the worker closure of src/orfs.rs:53-104:
+ * start_stop_codon_indices_by_frame_naive (lib/src/orfs.rs:73) + find_orfs_with_indices (:149) + the filter +
+ * longest_orfs (:301), once per strand.  Device pointers; the call only enqueues work on the ctx stream.
+ *   d_orf_offsets  uint64[n_records + 1], always written in full: record i's ORFs are
+ *                  d_orfs[d_orf_offsets[i] .. d_orf_offsets[i+1]), its forward ORFs before its reverse ones
+ *   d_orfs         `capacity` descriptors; a record whose ORFs do not all fit below capacity is not written
+ * Records of 0 or 1 symbols (a panic in the reference) have no ORFs; records of 2^32 symbols or more are not processed.
+ * offsets[0] need not be 0. */
+int circkit_orfs_batch_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                              const circkit_orf_params* params, uint64_t* d_orf_offsets, circkit_orf* d_orfs,
+                              uint64_t capacity);
+/* Waits for the most recent ORF batch of this ctx (device or host form) and sets *total = its total number of ORFs
+ * (d_orf_offsets[n_records]); CIRCKIT_ERR_OOM when that is more than the capacity it was given. */
+int circkit_orfs_status(circkit_ctx* ctx, uint64_t* total);
+/* The same with HOST buffers; synchronizes.  orf_offsets (n_records + 1) and *total are always written; when
+ * *total > capacity nothing is written to orfs and the call returns CIRCKIT_ERR_OOM, so that the caller can grow its
+ * buffer and call again.  offsets[0] must be 0. */
+int circkit_orfs_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                       const circkit_orf_params* params, uint64_t* orf_offsets, circkit_orf* orfs, uint64_t capacity,
+                       uint64_t* total);
+/* pub fn find_orfs(seq: &str) -> Vec<Orf>         lib/src/orfs.rs:41
+ * ATG / TAA,TAG,TGA, forward strand, no filter, find order; the bytes are compared as given (no normalization).
+ * *count = the number of ORFs; CIRCKIT_ERR_OOM (and nothing in out) when it is more than capacity. */
+int circkit_find_orfs(circkit_ctx* ctx, const uint8_t* s, size_t n, circkit_orf* out, size_t capacity, size_t* count);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
