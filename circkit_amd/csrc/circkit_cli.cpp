@@ -893,7 +893,7 @@ int run_orfs(const Options& opt, Input& in, Output& out)
                     id += std::to_string(f.start);
                     ckhost::csv_field(row, (const uint8_t*)id.data(), id.size(), delim);
                     row += delim;
-                    if (hl) ckhost::csv_field(row, hp, hl, delim);
+                    ckhost::csv_field(row, hp, hl, delim);
                     row += delim;
                     row += std::to_string(t_start);
                     row += delim;
@@ -996,6 +996,7 @@ int main(int argc, char** argv)
     Input in = open_input(opt);
     Output out = open_output(opt);
     if (opt.cmd == "rotate" || opt.cmd == "cat" || opt.cmd == "decat") return run_host_edit(opt, in, out);
+    if (getenv("CIRCKIT_CLI_CHUNK_MB")) { const int m = atoi(getenv("CIRCKIT_CLI_CHUNK_MB")); if (m >= 1 && m <= 1024) Pipeline::CHUNK = (size_t)m << 20; }
     if (opt.cmd == "orfs") return run_orfs(opt, in, out);
     FILE* table = nullptr;
     char delim = ',';
@@ -1017,7 +1018,6 @@ int main(int argc, char** argv)
     if (n_parsers < 1) n_parsers = 1;
     if (n_parsers > 64) n_parsers = 64;          // (beyond that the six chunk slots in flight are the limit, not the threads)
     if (getenv("CIRCKIT_CLI_SLOTS")) { const int k = atoi(getenv("CIRCKIT_CLI_SLOTS")); if (k >= 2 && k <= Pipeline::MAX_K) Pipeline::K = k; }
-    if (getenv("CIRCKIT_CLI_CHUNK_MB")) { const int m = atoi(getenv("CIRCKIT_CLI_CHUNK_MB")); if (m >= 1 && m <= 1024) Pipeline::CHUNK = (size_t)m << 20; }
     static Pipeline P;
 
     for (Slot& sl : P.slot) {

@@ -4,7 +4,8 @@
 //   orfs_count_kernel   one lane per record runs orf_strand (orfs.h) on each requested strand and writes the count
 //   scan                exclusive prefix sum of the counts into d_orf_offsets (tile sums, one-workgroup scan, apply)
 //   orfs_emit_kernel    the same lane runs the same sweep again, writes the descriptors at its offset and sorts each
-//                       strand's run into the reference's output order (insertion sort up to 32, heapsort beyond)
+//                       strand's run into the reference's output order (orfs.h sort_run: insertion sort up to 32,
+//                       heapsort beyond)
 // A lane per record reads its record twice per strand (prologue + sweep) in each of the two passes; the bytes are L2-resident
 // between passes for the records of a workgroup.  Records of fewer than 2 symbols have no ORFs (the reference panics on
 // them; the CLI reports that itself), records of 2^32 symbols or more are not processed (none are produced).
@@ -67,38 +68,6 @@ __global__ __launch_bounds__(ORF_WG) void orfs_count_kernel(const uint8_t* __res
     orf_offsets[i + 1] = record_orfs(bytes + o, L, cls, A, nullptr, &nf);
 }
 
-__device__ void sort_run(Orf* a, uint32_t n, uint32_t mode)
-{
-    using ck_orfs::orf_before;
-    if (n <= 32) {
-        for (uint32_t i = 1; i < n; ++i) {
-            const Orf x = a[i];
-            uint32_t j = i;
-            for (; j > 0 && orf_before(x, a[j - 1], mode); --j) a[j] = a[j - 1];
-            a[j] = x;
-        }
-        return;
-    }
-    // heapsort, a max-heap under orf_before's reverse (the root is the element that goes last)
-    auto sift = [&](uint32_t root, uint32_t end) {
-        const Orf x = a[root];
-        for (;;) {
-            uint32_t child = 2 * root + 1;
-            if (child >= end) break;
-            if (child + 1 < end && orf_before(a[child], a[child + 1], mode)) ++child;
-            if (!orf_before(x, a[child], mode)) break;
-            a[root] = a[child];
-            root = child;
-        }
-        a[root] = x;
-    };
-    for (uint32_t r = n / 2; r-- > 0;) sift(r, n);
-    for (uint32_t end = n - 1; end > 0; --end) {
-        const Orf t = a[0]; a[0] = a[end]; a[end] = t;
-        sift(0, end);
-    }
-}
-
 __global__ __launch_bounds__(ORF_WG) void orfs_emit_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets,
                                                            uint64_t n, OrfArgs A, const uint64_t* __restrict__ orf_offsets,
                                                            Orf* __restrict__ orfs, uint64_t capacity)
@@ -109,12 +78,14 @@ __global__ __launch_bounds__(ORF_WG) void orfs_emit_kernel(const uint8_t* __rest
     const uint64_t i = (uint64_t)blockIdx.x * ORF_WG + threadIdx.x;
     if (i >= n) return;
     const uint64_t base = orf_offsets[i], end = orf_offsets[i + 1];
-    if (end == base || end > capacity) return;               // a record whose ORFs do not all fit is not written
+    // a record whose ORFs do not all fit is not written; end < base (offsets that a failed scan left falling) is not
+    // either, where (end - base) - nf below would wrap and the sort would run far past the buffer
+    if (end <= base || end > capacity) return;
     const uint64_t o = offsets[i], L = offsets[i + 1] - o;
     uint32_t nf;
     record_orfs(bytes + o, L, cls, A, orfs + base, &nf);
-    sort_run(orfs + base, nf, A.F.mode);
-    sort_run(orfs + base + nf, (uint32_t)(end - base) - nf, A.F.mode);
+    ck_orfs::sort_run(orfs + base, nf, A.F.mode);
+    ck_orfs::sort_run(orfs + base + nf, (uint32_t)(end - base) - nf, A.F.mode);
 }
 
 // ---- exclusive scan of uint64 counts, in place: a[0..n) (a[-1] is the 0 the count kernel wrote) ----

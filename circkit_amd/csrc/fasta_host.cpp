@@ -189,9 +189,12 @@ void place_sub_batch(const Batch& sub, size_t start, uint64_t rec0, uint64_t byt
     }
 }
 
+// The csv crate's QuoteStyle::Necessary: a field is quoted when it holds the delimiter, '"', '\n' or '\r', its quotes
+// doubled.  An empty field is written bare; only a record of one empty field is written as "", and every table row here
+// has two fields or more.
 void csv_field(std::string& out, const uint8_t* p, size_t n, char delim)
 {
-    bool quote = n == 0;
+    bool quote = false;
     for (size_t i = 0; i < n && !quote; ++i) quote = p[i] == (uint8_t)delim || p[i] == '"' || p[i] == '\n' || p[i] == '\r';
     if (!quote) { out.append((const char*)p, n); return; }
     out.push_back('"');

@@ -74,8 +74,8 @@ inline Span record_id(const uint8_t* text, Span head)
     return Span{ head.off, k };
 }
 
-// csv crate field quoting (QuoteStyle::Necessary): quote when the field holds the delimiter, a quote, CR or LF
-// (or is empty); quotes are doubled.
+// csv crate field quoting (QuoteStyle::Necessary) of one field of a record of two fields or more: quote when the field
+// holds the delimiter, a quote, CR or LF; quotes are doubled; an empty field is written bare.
 void csv_field(std::string& out, const uint8_t* p, size_t n, char delim);
 
 }  // namespace ckhost

@@ -29,7 +29,7 @@
 // frame(s) before, in chain order: k laps back).  The None key is one group across frames: every member has the same
 // length and wraps, and longest_orfs keeps the one that comes last in find order (highest frame, then highest start).
 //
-// The emitted ORFs of a strand are in no particular order; the caller sorts them (orf_before).
+// The emitted ORFs of a strand are in no particular order; the caller sorts them (sort_run).
 #pragma once
 #include <stdint.h>
 
@@ -64,12 +64,47 @@ __device__ inline bool passes(const Filter& F, uint64_t length, uint32_t stop, u
 
 // the order of longest_orfs' output (stable ascending sort by length, reversed): length, then frame, then start, all
 // descending; mode 1 = find order (frame-major, start ascending)
-__device__ inline bool orf_before(const Orf& a, const Orf& b, uint32_t mode)
+__host__ __device__ inline bool orf_before(const Orf& a, const Orf& b, uint32_t mode)
 {
     const uint32_t fa = a.start % 3, fb = b.start % 3;
     if (mode == 1) return fa != fb ? fa < fb : a.start < b.start;
     if (a.length != b.length) return a.length > b.length;
     return fa != fb ? fa > fb : a.start > b.start;
+}
+
+constexpr uint32_t SORT_INSERTION_MAX = 32;   // runs up to this many ORFs sort by insertion, longer ones by heapsort
+
+// Sorts one strand's run of a record into orf_before's order, in place and without scratch memory (one lane of the emit
+// kernel; the host build of the lane routine calls it too).
+__host__ __device__ inline void sort_run(Orf* a, uint32_t n, uint32_t mode)
+{
+    if (n <= SORT_INSERTION_MAX) {
+        for (uint32_t i = 1; i < n; ++i) {
+            const Orf x = a[i];
+            uint32_t j = i;
+            for (; j > 0 && orf_before(x, a[j - 1], mode); --j) a[j] = a[j - 1];
+            a[j] = x;
+        }
+        return;
+    }
+    // heapsort, a max-heap under orf_before's reverse (the root is the element that goes last)
+    auto sift = [&](uint32_t root, uint32_t end) {
+        const Orf x = a[root];
+        for (;;) {
+            uint32_t child = 2 * root + 1;
+            if (child >= end) break;
+            if (child + 1 < end && orf_before(a[child], a[child + 1], mode)) ++child;
+            if (!orf_before(x, a[child], mode)) break;
+            a[root] = a[child];
+            root = child;
+        }
+        a[root] = x;
+    };
+    for (uint32_t r = n / 2; r-- > 0;) sift(r, n);
+    for (uint32_t end = n - 1; end > 0; --end) {
+        const Orf t = a[0]; a[0] = a[end]; a[end] = t;
+        sift(0, end);
+    }
 }
 
 // symbol j of the strand (REV: the reverse complement of the record)

@@ -280,6 +280,17 @@ def cli_decat(data):
     return b"".join(b">" + h + b"\n" + full_seq(r)[:len(full_seq(r)) // 2] + b"\n" for h, r in _read_until_error(data))
 
 
+def csv_row(fields, delimiter):
+    """One row of a table written by the csv crate (QuoteStyle::Necessary) with two fields or more: a field is quoted when
+    it holds the delimiter, '"', '\\n' or '\\r', its quotes doubled; an empty field is written bare."""
+    out = []
+    for f in fields:
+        if delimiter in f or b'"' in f or b"\n" in f or b"\r" in f:
+            f = b'"' + f.replace(b'"', b'""') + b'"'
+        out.append(f)
+    return delimiter.join(out) + b"\n"
+
+
 def cli_uniq(data, canonical_out=False, delimiter=b","):
     """src/uniq.rs:24-83; returns (fasta_bytes, table_bytes)."""
     seen = {}
@@ -293,6 +304,6 @@ def cli_uniq(data, canonical_out=False, delimiter=b","):
             seen[h] = rid
             out.append(b">" + head + b"\n" + (canon if canonical_out else seq) + b"\n")
         else:
-            rows.append(seen[h] + delimiter + rid + b"\n")
+            rows.append(csv_row([seen[h], rid], delimiter))
     table = (b"id" + delimiter + b"duplicate_id\n" + b"".join(rows)) if rows else b""
     return b"".join(out), table

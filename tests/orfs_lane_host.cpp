@@ -1,5 +1,5 @@
-// orfs_lane_host.cpp -- TEST INFRASTRUCTURE ONLY: the per-lane routine of circkit_amd/csrc/orfs.h (orf_strand + the
-// output order) compiled for the host, so that tests/test_orfs_cpu.py can check the kernel's logic against the
+// orfs_lane_host.cpp -- TEST INFRASTRUCTURE ONLY: the per-lane routine of circkit_amd/csrc/orfs.h (orf_strand + sort_run)
+// compiled for the host, so that tests/test_orfs_cpu.py can check the kernel's logic against the
 // restatement (tests/orfs_ref.c) on a machine without a GPU.  A lane of orfs_count_kernel / orfs_emit_kernel touches
 // nothing but its own record, so this is the kernel's computation, record for record.  Built by tests/orfs_ref.py.
 #include <stdint.h>
@@ -48,7 +48,7 @@ extern "C" uint64_t ck_lane_orfs_batch(const uint8_t* bytes, const uint64_t* off
                 const size_t b = v.size();
                 if (st == 0) ck_orfs::orf_strand<false>(s, (uint32_t)L, cls, F, 0, put);
                 else ck_orfs::orf_strand<true>(s, (uint32_t)L, cls, F, 1, put);
-                std::sort(v.begin() + b, v.end(), [&](const Orf& x, const Orf& y) { return ck_orfs::orf_before(x, y, F.mode); });
+                ck_orfs::sort_run(v.data() + b, (uint32_t)(v.size() - b), F.mode);      // the emit kernel's sort
             }
         }
         if (out) std::copy(v.begin(), v.end(), out + out_off[i]);

@@ -153,28 +153,52 @@ def ryu_f64(x):
     return r
 
 
+def cyclic_cut(src, start, n):
+    """Orf::seq: n bytes of src read cyclically from start (n may exceed len(src))."""
+    if n <= 0 or not src:
+        return b""
+    s = start % len(src)
+    out = src[s:s + n]
+    while len(out) < n:
+        out += src[:n - len(out)]
+    return out
+
+
 def cli_orfs(data, min_length=75, start_codons="ATG", stop_codons="TAA,TAG,TGA", include_stop=False, no_stop_required=False,
-             min_wraps=0, max_wraps=3, strand="both", min_ratio=0.0, table_delim=None):
+             min_wraps=0, max_wraps=3, strand="both", min_ratio=0.0, table_delim=None, threads=16):
     """Returns (fasta_bytes, table_bytes|None).  Raises ValueError on a record of fewer than 2 symbols (the reference's
-    panic)."""
+    panic).  Table fields are quoted as the csv crate does (oracle.csv_row)."""
     from oracle import oracle as O
     strands = 1 if strand == "forward" else 3          # --strand reverse prints both lists too (src/orfs.rs:79-103)
     kw = dict(start_codons=start_codons.split(","), stop_codons=stop_codons.split(","), min_length=min_length,
               min_ratio=min_ratio, min_wraps=min_wraps, max_wraps=max_wraps, require_stop=not no_stop_required,
               strands=strands, mode=0)
-    out, rows = [], []
-    cut = 0 if include_stop else 3
+    recs = []
     for head, raw in O.read_fasta(data):
         norm, _ = O.normalize(raw)
         if len(norm) < 2:
             raise ValueError("record of %d symbols" % len(norm))
+        recs.append((head, raw, norm))
+    # the worker closure for every record at once (threaded), then the writer closure record by record
+    norms = [r[2] for r in recs]
+    offs = np.zeros(len(recs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(x) for x in norms])
+    joined = np.frombuffer(b"".join(norms) + b"\0", dtype=np.uint8)[:int(offs[-1])]
+    orf_off, orfs = orfs_batch(joined, offs, threads=threads, **kw)
+    out, rows = [], []
+    cut = 0 if include_stop else 3
+    for i, (head, raw, norm) in enumerate(recs):
+        o0, o1 = int(orf_off[i]), int(orf_off[i + 1])
+        if o0 == o1:
+            continue
         full = O.full_seq(raw)
         rc = O.revcomp(norm)
         L = len(norm)
-        for (start, stop, wraps, length, st) in orfs_record(norm, **kw):
+        for r in orfs[o0:o1]:
+            start, length, wraps, st = int(r["start"]), int(r["length"]), int(r["wraps"]), int(r["strand"])
+            stop = None if int(r["stop"]) == NONE else int(r["stop"])
             src = full if st == 0 else rc
-            n = length - cut
-            seq = bytes(src[(start + k) % len(src)] for k in range(n)) if n > 0 else b""
+            seq = cyclic_cut(src, start, length - cut)
             tag = b"_ORF" if st == 0 else b"_RC_ORF"
             orf_id = head + tag + str(start).encode()
             out.append(b">" + orf_id + b"\n" + seq + b"\n")
@@ -185,7 +209,7 @@ def cli_orfs(data, min_length=75, start_codons="ATG", stop_codons="TAA,TAG,TGA",
                     t_start, t_stop = start, stop
                 fields = [orf_id, head, str(t_start).encode(), b"" if t_stop is None else str(t_stop).encode(),
                           str(length - cut).encode(), str(wraps).encode(), ryu_f64(length / len(full)).encode()]
-                rows.append(table_delim.join(fields) + b"\n")
+                rows.append(O.csv_row(fields, table_delim))
     table = None
     if table_delim is not None:
         table = (table_delim.join([b"orf_id", b"seq_id", b"start", b"stop", b"length", b"wraps", b"ratio"]) + b"\n" +

@@ -170,3 +170,143 @@ def test_library_exports_the_orf_entry_points():
         assert hasattr(lib, s), s
     p = circkit_amd.orf_params(start_codons=["ATG", "CTG", "AT"], strands="both", mode="all")
     assert (p.n_start_codons, p.n_stop_codons, p.strands, p.mode) == (2, 3, 3, 1)
+
+
+# ---- the ORF kernels' edges, the emit kernel's sort and the filter boundaries, on the host build -------------------------
+CSRC = os.path.join(ROOT, "circkit_amd", "csrc")
+# the record counts of tests/test_orfs_gpu_edges.py test_scan_edges_every_record: both sides of a workgroup of the count and
+# emit kernels (ORF_WG), of a scan tile (SCAN_TILE records) and of one chunk of SCAN_WG tile sums in scan_sums, then a
+# second chunk of one tile and a third chunk
+SCAN_COUNTS = [1, 255, 256, 257, 8191, 8192, 8193, 8_388_607, 8_388_608, 8_388_609, 16_777_217]
+# the ORFs per strand of sort_switch_records: both sides of sort_run's switch from insertion sort to heapsort, and heapsort
+SORT_COUNTS = [31, 32, 33, 64, 3000]
+
+
+def kernel_constants():
+    """ORF_WG, SCAN_WG, SCAN_ITEMS (circkit_orfs.hip), SORT_INSERTION_MAX (orfs.h), and SCAN_TILE = SCAN_WG * SCAN_ITEMS."""
+    import re
+    src = open(os.path.join(CSRC, "circkit_orfs.hip")).read() + open(os.path.join(CSRC, "orfs.h")).read()
+    c = {}
+    for name in ("ORF_WG", "SCAN_WG", "SCAN_ITEMS", "SORT_INSERTION_MAX"):
+        m = re.search(r"\b%s\s*=\s*(\d+)" % name, src)
+        assert m, name
+        c[name] = int(m.group(1))
+    c["SCAN_TILE"] = c["SCAN_WG"] * c["SCAN_ITEMS"]
+    return c
+
+
+def test_edge_counts_straddle_the_kernel_edges():
+    """If a launch or sort constant of the ORF kernels changes, SCAN_COUNTS / SORT_COUNTS above must move with it."""
+    c = kernel_constants()
+    chunk = c["SCAN_WG"] * c["SCAN_TILE"]
+    for name, edge in (("ORF_WG", c["ORF_WG"]), ("SCAN_TILE", c["SCAN_TILE"]), ("one chunk of tile sums", chunk)):
+        assert {edge - 1, edge, edge + 1} <= set(SCAN_COUNTS), ("SCAN_COUNTS", name, edge)
+    assert 1 in SCAN_COUNTS and 2 * chunk < max(SCAN_COUNTS) <= 2 * chunk + c["SCAN_TILE"], "SCAN_COUNTS: a third chunk"
+    b = c["SORT_INSERTION_MAX"]
+    assert {b - 1, b, b + 1} <= set(SORT_COUNTS) and max(SORT_COUNTS) > 1000, ("SORT_COUNTS", b)
+
+
+def revcomp(s):
+    return s[::-1].translate(bytes.maketrans(b"ACGT", b"TGCA"))
+
+
+def sort_switch_records():
+    """Records with runs of exactly SORT_COUNTS ORFs per strand in both modes (min_length 0, no other filter).  Each unit is
+    a start with its own stop (ATG TAA, ATG AAA TAA, ATG CCC TGA), 7, 10 or 11 symbols long, so the starts fall in every
+    frame and many ORFs share a length across frames: heapsort must break those ties by frame, then start.  Each record
+    comes with its reverse complement, which puts the same run on the reverse strand."""
+    rng = random.Random(91)
+    units = [b"ATGTAAC", b"ATGAAATAAC", b"ATGCCCTGAGG"]
+    out = []
+    for k in SORT_COUNTS:
+        for s in (b"".join(rng.choice(units) for _ in range(k)), units[0] * k):
+            out += [s, revcomp(s)]
+    return out
+
+
+def test_lane_sort_switch():
+    """sort_run (orfs.h), the emit kernel's sort, through the host build: every run size of SORT_COUNTS on both strands in
+    both modes, with length ties across all three frames, against the restatement."""
+    seqs = sort_switch_records()
+    d, o = _pack(seqs)
+    for mode in (0, 1):
+        for strands in (1, 2, 3):
+            eo, e = R.orfs_batch(d, o, mode=mode, strands=strands)
+            go, g = R.lane_orfs_batch(d, o, mode=mode, strands=strands)
+            assert np.array_equal(eo, go) and np.array_equal(e, g), (mode, strands)
+        runs = {(st, int(np.sum(e["strand"][eo[i]:eo[i + 1]] == st))) for i in range(len(seqs)) for st in (0, 1)}
+        for k in SORT_COUNTS:
+            assert (0, k) in runs and (1, k) in runs, (mode, k)
+        frames = {}
+        for i in range(len(seqs)):
+            for r in e[eo[i]:eo[i + 1]]:
+                frames.setdefault((i, int(r["strand"]), int(r["length"])), set()).add(int(r["start"]) % 3)
+        assert any(len(f) == 3 for f in frames.values()), mode
+
+
+def _around(x):
+    import math
+    return (math.nextafter(x, -math.inf), x, math.nextafter(x, math.inf))
+
+
+def filter_boundary_cases():
+    """(records, params, chosen (length, L) pairs) at the exact edges of each filter of orfs.h passes(), in both modes.
+    The records have prime lengths near 1000, so length / L is not dyadic.  min_ratio sits at length / L (correctly
+    rounded) and at its two neighbours for the chosen ORFs; for most of them `length / L >= r` and `length >= r * L`
+    disagree at one of the three.  min_length sits at length - 3, one either side of it, and near 2^64.  min_wraps is above
+    max_wraps, and max_wraps is 4 and 2^32 - 1."""
+    rng = random.Random(101)
+    primes = [p for p in range(960, 1300) if all(p % q for q in range(2, 37))][:24]
+    seqs = [bytes(rng.choice(b"ACGT") for _ in range(p)) for p in primes]
+    d, o = _pack(seqs)
+    eo, e = R.orfs_batch(d, o, mode=1)
+    pairs = sorted({(int(e["length"][k]), len(seqs[i])) for i in range(len(seqs)) for k in range(int(eo[i]), int(eo[i + 1]))})
+    split = [(l, L) for l, L in pairs if any((l / L >= r) != (l >= r * L) for r in _around(l / L))]
+    chosen = split[::max(1, len(split) // 6)][:6] + random.Random(102).sample(pairs, 4)
+    cases = []
+    for mode in (0, 1):
+        for l, L in chosen:
+            cases += [dict(mode=mode, min_ratio=r) for r in _around(l / L)]
+            cases += [dict(mode=mode, min_length=m) for m in (l - 4, l - 3, l - 2) if m >= 0]
+        cases += [dict(mode=mode, min_length=m) for m in (2 ** 64 - 3, 2 ** 64 - 2, 2 ** 64 - 1)]
+        cases += [dict(mode=mode, min_wraps=a, max_wraps=b) for a, b in ((1, 0), (2, 1), (3, 2), (4, 3), (0, 4), (2, 4),
+                                                                          (0, 2 ** 32 - 1), (3, 2 ** 32 - 1), (4, 2 ** 32 - 1))]
+    return seqs, cases, chosen
+
+
+def test_filter_boundaries_are_sharp():
+    """The boundary cases are not vacuous: the kept set changes across each ratio and each length boundary, chosen ORFs
+    tell `length / L >= r` from `length >= r * L`, and min_length near 2^64 or min_wraps > max_wraps keeps nothing."""
+    import math
+    seqs, _, chosen = filter_boundary_cases()
+    d, o = _pack(seqs)
+
+    def kept(**kw):
+        return len(R.orfs_batch(d, o, mode=1, **kw)[1])
+    for l, L in chosen:
+        r = l / L
+        assert r * 2 ** 20 != math.floor(r * 2 ** 20), (l, L)          # not dyadic
+        assert kept(min_ratio=r) > kept(min_ratio=math.nextafter(r, math.inf)), (l, L)
+        assert kept(min_length=l - 3) > kept(min_length=l - 2), (l, L)
+    assert sum(any((l / L >= x) != (l >= x * L) for x in _around(l / L)) for l, L in chosen) >= 5
+    assert kept() > 0 and kept(min_length=2 ** 64 - 1) == 0 and kept(min_wraps=2, max_wraps=1) == 0
+
+
+def test_lane_filter_boundaries():
+    seqs, cases, _ = filter_boundary_cases()
+    d, o = _pack(seqs)
+    for kw in cases:
+        eo, e = R.orfs_batch(d, o, **kw)
+        go, g = R.lane_orfs_batch(d, o, **kw)
+        assert np.array_equal(eo, go) and np.array_equal(e, g), kw
+
+
+def test_csv_row_and_cyclic_cut():
+    """The writer restatements: the csv crate's quoting (oracle.csv_row) and Orf::seq's cyclic cut."""
+    from oracle import oracle as O
+    assert O.csv_row([b"a", b"", b"b"], b",") == b"a,,b\n"
+    assert O.csv_row([b"", b""], b",") == b",\n"
+    assert O.csv_row([b"a,b", b'q"t', b"x\ty"], b",") == b'"a,b","q""t",x\ty\n'
+    assert O.csv_row([b"a,b", b"x\ty", b"c\rd", b"e\nf"], b"\t") == b'a,b\t"x\ty"\t"c\rd"\t"e\nf"\n'
+    assert R.cyclic_cut(b"ABCDE", 3, 12) == b"DEABCDEABCDE"
+    assert R.cyclic_cut(b"ABCDE", 7, 2) == b"CD" and R.cyclic_cut(b"ABCDE", 1, 0) == b""
