@@ -2,7 +2,17 @@
 
 csrc/      hand-written HIP kernels + the C ABI (include/circkit.h) + the C++ FASTA host
 api.py     ctypes mirror of the reference's lib-crate API over that C ABI
+monomerize.py  `circkit monomerize` over the GPU batch call (also `python -m circkit_amd.monomerize`); the module is
+           callable: circkit_amd.monomerize(s, ...) is Monomerizer::monomerize on one record
 """
 from .api import (CirckitError, Context, canonicalize, default_context, find_orfs, lmsr, lmsr_index, load_library,  # noqa: F401
-                  normalize, orf_params, xxh3_64)
+                  monomer_end_index, monomerize_params, normalize, orf_params, xxh3_64)
 from . import uniq  # noqa: F401,E402
+
+
+def __getattr__(name):
+    # loaded on first use, so that `python -m circkit_amd.monomerize` does not find its module imported already
+    if name == "monomerize":
+        import importlib
+        return importlib.import_module(".monomerize", __name__)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

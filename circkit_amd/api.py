@@ -4,6 +4,8 @@
     circkit::lmsr(&[u8]) -> Vec<u8>          lib/src/canonicalize.rs:41   -> lmsr(b)
     circkit::canonicalize(&[u8]) -> Vec<u8>  lib/src/canonicalize.rs:54   -> canonicalize(b)
     xxhash_rust::xxh3::xxh3_64               call site src/uniq.rs:45     -> xxh3_64(b)
+    Monomerizer::last_monomer_end_index[_sensitive]  lib/src/monomerize.rs:97, :122  -> monomer_end_index(b, ...)
+    Monomerizer::monomerize[_sensitive]      lib/src/monomerize.rs:138, :146 -> monomerize(b, ...)
 
 Everything computes on the GPU through libcirckit_hip.so; there is no CPU fallback -- importing works
 without a GPU (so the ABI can be inspected), creating a Context does not.
@@ -70,6 +72,9 @@ SIGNATURES = {
     "circkit_orfs_status": (_i, [_vp, ctypes.POINTER(_u64)]),
     "circkit_orfs_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
     "circkit_find_orfs": (_i, [_vp, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
+    "circkit_monomerize_batch_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "circkit_monomerize_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "circkit_monomer_end_index": (_i, [_vp, _vp, _sz, _vp, ctypes.POINTER(_sz), ctypes.POINTER(_i)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -114,6 +119,32 @@ def orf_params(start_codons=("ATG",), stop_codons=("TAA", "TAG", "TGA"), min_len
 def _orf_arrays(offsets, orfs):
     return {"offsets": offsets, "start": orfs["start"].copy(), "stop": orfs["stop"].copy(), "length": orfs["length"].copy(),
             "wraps": orfs["wraps"].copy(), "strand": orfs["strand"].copy()}
+
+
+# circkit_monomerize_params (include/circkit.h)
+MONOMER_NONE = 0xFFFFFFFF
+BOTH_CUTOFFS = ("Both overlap_dist and overlap_min_identity are set. They are mutually exclusive since they may produce "
+                "conflicting filtering results.")
+
+
+class MonomerizeParams(ctypes.Structure):
+    _fields_ = [("seed_len", _u32), ("use_identity", _u32), ("overlap_dist", _u64), ("min_identity", ctypes.c_double),
+                ("sensitive", _u32)]
+
+
+def monomerize_params(seed_len=10, max_mismatch=None, min_identity=None, sensitive=False):
+    """circkit_monomerize_params from Python values (MonomerizerBuilder: lib/src/monomerize.rs:19-41).  Setting both
+    cut-offs raises ValueError with the builder's message; neither = no mismatch allowed.  The seed length and the identity
+    are checked by the library (CIRCKIT_ERR_INVALID_ARG)."""
+    if max_mismatch is not None and min_identity is not None:
+        raise ValueError(BOTH_CUTOFFS)
+    p = MonomerizeParams()
+    p.seed_len = int(seed_len) if 0 <= int(seed_len) < 2 ** 32 else 0
+    p.use_identity = int(min_identity is not None)
+    p.overlap_dist = int(max_mismatch or 0)
+    p.min_identity = float(min_identity) if min_identity is not None else 0.0
+    p.sensitive = int(bool(sensitive))
+    return p
 
 
 _lib = None
@@ -360,6 +391,42 @@ class Context:
             return [(int(o["start"]), None if int(o["stop"]) == ORF_NO_STOP else int(o["stop"]), int(o["wraps"]), int(o["length"]))
                     for o in out[:cnt.value]]
 
+    # -- monomerize -----------------------------------------------------------------------------
+    def monomerize_batch_device(self, d_bytes, d_offsets, n_records, d_end, params=None, **kw):
+        """Enqueues circkit_monomerize_batch_device: d_end (uint32[n_records], device) gets every record's end index or
+        MONOMER_NONE once the ctx stream has run past it."""
+        p = params if params is not None else monomerize_params(**kw)
+        self._check(self._lib.circkit_monomerize_batch_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records),
+                                                              ctypes.byref(p), _ptr(d_end)))
+
+    def monomerize_batch(self, data, offsets, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False):
+        """End index of the first monomer of every record of a host CSR batch: a uint32 array, MONOMER_NONE where the
+        reference returns None (last_monomer_end_index, or its sensitive form)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        p = monomerize_params(seed_len, max_mismatch, min_identity, sensitive)
+        out = np.full(max(n, 1), MONOMER_NONE, dtype=np.uint32)
+        self._check(self._lib.circkit_monomerize_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n,
+                                                       ctypes.byref(p), _ptr(out)))
+        return out[:n]
+
+    def monomer_end_index(self, s, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False):
+        """lib/src/monomerize.rs:97 / :122 on any bytes: the end index, or None."""
+        s = bytes(s)
+        buf = ctypes.create_string_buffer(s, max(len(s), 1))
+        p = monomerize_params(seed_len, max_mismatch, min_identity, sensitive)
+        end, found = _sz(0), _i(0)
+        self._check(self._lib.circkit_monomer_end_index(self._h, ctypes.addressof(buf), len(s), ctypes.byref(p),
+                                                        ctypes.byref(end), ctypes.byref(found)))
+        return end.value if found.value else None
+
+    def monomerize(self, s, **kw):
+        """Monomerizer::monomerize / monomerize_sensitive (lib/src/monomerize.rs:138, :146): the monomer's bytes."""
+        s = bytes(s)
+        e = self.monomer_end_index(s, **kw)
+        return s if e is None else s[:e]
+
     # -- single record: the lib-crate API --------------------------------------------------------
     def _single(self, fn, s):
         s = bytes(s)
@@ -428,6 +495,14 @@ def xxh3_64(s):
 
 def find_orfs(s):
     return default_context().find_orfs(s)
+
+
+def monomer_end_index(s, **kw):
+    return default_context().monomer_end_index(s, **kw)
+
+
+def monomerize(s, **kw):
+    return default_context().monomerize(s, **kw)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

@@ -1256,6 +1256,8 @@ struct circkit_ctx {
 
     void* orfs = nullptr;                     // circkit_orfs.hip's buffers, freed by the function it registers with them
     void (*orfs_release)(void*) = nullptr;
+    void* monomerize = nullptr;               // circkit_monomerize.hip's staging buffers, likewise
+    void (*monomerize_release)(void*) = nullptr;
 };
 
 // circkit_orfs.hip's view of the ctx
@@ -1263,6 +1265,7 @@ hipStream_t ck_ctx_stream(circkit_ctx* c) { return c->stream; }
 int ck_ctx_device(circkit_ctx* c) { return c->device; }
 int ck_ctx_fail(circkit_ctx* c, int code, const char* msg) { c->err = msg; return code; }
 void** ck_ctx_orfs_slot(circkit_ctx* c, void (*release)(void*)) { c->orfs_release = release; return &c->orfs; }
+void** ck_ctx_monomerize_slot(circkit_ctx* c, void (*release)(void*)) { c->monomerize_release = release; return &c->monomerize; }
 
 namespace {
 
@@ -1947,6 +1950,7 @@ int circkit_ctx_destroy(circkit_ctx* c)
     if (c->h_mode) (void)hipHostFree((void*)c->h_mode);
     if (c->h_off) (void)hipHostFree((void*)c->h_off);
     if (c->orfs_release) c->orfs_release(c->orfs);
+    if (c->monomerize_release) c->monomerize_release(c->monomerize);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return CIRCKIT_OK;

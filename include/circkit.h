@@ -255,6 +255,43 @@ int circkit_orfs_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* o
  * *count = the number of ORFs; CIRCKIT_ERR_OOM (and nothing in out) when it is more than capacity. */
 int circkit_find_orfs(circkit_ctx* ctx, const uint8_t* s, size_t n, circkit_orf* out, size_t capacity, size_t* count);
 
+/* ---- monomerize (`circkit monomerize`) ------------------------------------------------------------ */
+#define CIRCKIT_MONOMER_NONE 0xFFFFFFFFu     /* end index: None (the record is no multimer under the settings) */
+/* The Monomerizer's settings (lib/src/monomerize.rs:6-17; `--seed-length`, `--max-mismatch`, `--min-identity`,
+ * `--sensitive` of src/commands.rs):
+ *   seed_len       1..63 (MonomerizerBuilder::validate, lib/src/monomerize.rs:27-37); anything else: INVALID_ARG
+ *   use_identity   0: an overlap may hold up to overlap_dist mismatches; 1: up to
+ *                  ovl - floor(ovl * min_identity) of its ovl symbols (:70-76, the product in f64).  The two exclude
+ *                  each other in the reference, hence the switch.
+ *   min_identity   in [0, 1] when used (src/monomerize.rs:40-44); NaN and anything outside: INVALID_ARG
+ *   sensitive      last_monomer_end_index_sensitive (:122) instead of last_monomer_end_index (:97) */
+typedef struct circkit_monomerize_params {
+    uint32_t seed_len;
+    uint32_t use_identity;
+    uint64_t overlap_dist;
+    double min_identity;
+    uint32_t sensitive;
+} circkit_monomerize_params;
+
+/* Replaces, for a whole batch of normalized records, the call of the worker closure of src/monomerize.rs:85-88:
+ * Monomerizer::last_monomer_end_index / last_monomer_end_index_sensitive (lib/src/monomerize.rs:97, :122).
+ * Device pointers; the call only enqueues work on the ctx stream.
+ *   d_end   uint32[n_records]: record i's monomer is its first d_end[i] symbols; CIRCKIT_MONOMER_NONE = None
+ * Nothing else is written (the monomer is a prefix of the input).  The worker's pre-check (a record shorter than the
+ * seed or than --min-length) and the writer's filters are the caller's.  Records of 2^32 symbols or more are not
+ * processed (NONE).  offsets[0] need not be 0.  The bytes are compared as given. */
+int circkit_monomerize_batch_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                                    uint64_t n_records, const circkit_monomerize_params* params, uint32_t* d_end);
+/* The same with HOST buffers; synchronizes.  offsets[0] must be 0; a record of 2^32 symbols or more:
+ * CIRCKIT_ERR_TOO_LONG and nothing is computed. */
+int circkit_monomerize_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                             const circkit_monomerize_params* params, uint32_t* end);
+/* pub fn last_monomer_end_index(self, seq: &[u8]) -> Option<usize>             lib/src/monomerize.rs:97
+ * pub fn last_monomer_end_index_sensitive(&self, seq: &[u8]) -> Option<usize>  lib/src/monomerize.rs:122
+ * *found = 0 for None, and then *end = n, so that s[..*end] is Monomerizer::monomerize[_sensitive] (:138, :146). */
+int circkit_monomer_end_index(circkit_ctx* ctx, const uint8_t* s, size_t n, const circkit_monomerize_params* params,
+                              size_t* end, int* found);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
