@@ -323,6 +323,15 @@ class Context:
         """Waits for the queued table work; raises CirckitError (OOM) if keys found no slot."""
         self._check(self._lib.circkit_uniq_status(self._h, None))
 
+    def uniq_overflowed(self):
+        """Waits like uniq_status; returns how many inserted records found no slot for their key (0: the table took them all)
+        instead of raising for an overflow.  Lookups answer ~0 for such keys until the next uniq_reset."""
+        n = _u32(0)
+        rc = self._lib.circkit_uniq_status(self._h, ctypes.byref(n))
+        if rc != OK and not (rc == -5 and n.value):
+            self._check(rc)
+        return n.value
+
     # -- host batches (numpy) -------------------------------------------------------------------
     def canonicalize_batch(self, data, offsets, want_bytes=True, want_index=False, want_strand=False,
                            want_xxh3=False):

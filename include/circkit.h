@@ -146,7 +146,13 @@ int circkit_xxh3_64(circkit_ctx* ctx, const uint8_t* s, size_t n, uint64_t* out_
  * The table persists in the ctx across calls until circkit_uniq_reset, so batches (and hash sets
  * gathered from other GPUs) can be folded in one after another:
  *   circkit_uniq_insert_device   folds (hash, global index) pairs into the table
- *   circkit_uniq_lookup_device   reads the winner for each hash */
+ *   circkit_uniq_lookup_device   reads the winner for each hash
+ * A lookup (lookup_device, lookup_rows) of a hash that is not in the table answers ~0 (UINT64_MAX), which is no record's
+ * index.  circkit_uniq_reset(expected_keys) sizes the table for that many DISTINCT keys (a power of two of at least 1024
+ * slots, at most 70 % full); the hash ~0 has a slot of its own beside them and never takes one.  When more distinct keys
+ * arrive than there are slots, the table fills completely, the records whose key found no slot are counted
+ * (circkit_uniq_status) and every lookup of such a key answers ~0; the keys that did find a slot keep their right
+ * answers.  circkit_uniq_reset clears the count with the table. */
 int circkit_uniq_reset(circkit_ctx* ctx, uint64_t expected_keys);
 int circkit_uniq_insert_device(circkit_ctx* ctx, const uint64_t* d_hash, uint64_t n, uint64_t base_index);
 /* the same with an explicit global index per key: the keys a rank receives in the multi-GPU exchange (hash-range
@@ -178,7 +184,7 @@ int circkit_uniq_gather_device(circkit_ctx* ctx, const uint64_t* d_answers, cons
 int circkit_uniq_resolve_device(circkit_ctx* ctx, const uint64_t* d_hash, uint64_t n, uint64_t base_index,
                                 uint64_t* d_first_seen, uint8_t* d_keep);
 /* reset / insert / lookup / resolve only enqueue work.  circkit_uniq_status waits for it and fails with CIRCKIT_ERR_OOM when
- * keys found no slot (more distinct keys than circkit_uniq_reset was told to expect); *n_overflowed (nullable) = how many. */
+ * keys found no slot (more distinct keys than circkit_uniq_reset was told to expect); *n_overflowed (nullable) = how many inserted records (not distinct keys) that were, 0 without an overflow. */
 int circkit_uniq_status(circkit_ctx* ctx, uint32_t* n_overflowed);
 
 /* Host-buffer form for streaming hosts (the CLI's batch loop): folds this batch's hashes (global indices

@@ -258,16 +258,7 @@ def test_host_batch_staging_grows_and_shrinks_with_the_batch(O):
     ctx.close()
 
 
-def _expected_first_seen(h):
-    """smallest index per value (numpy): order of first occurrence"""
-    order = np.argsort(h, kind="stable")
-    hs = h[order]
-    first_of_group = np.r_[True, hs[1:] != hs[:-1]]
-    group_first_idx = order[first_of_group]                     # stable sort: the first of each run is the smallest index
-    group_id = np.cumsum(first_of_group) - 1
-    fs = np.empty(len(h), dtype=np.int64)
-    fs[order] = group_first_idx[group_id]
-    return fs
+from tests.uniq_keys import expected_first_seen as _expected_first_seen       # smallest index per value (numpy)
 
 
 @pytest.mark.parametrize("shape", ["random", "empty_key", "one_bucket", "all_equal", "small", "threshold", "beyond"])

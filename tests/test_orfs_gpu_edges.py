@@ -20,7 +20,12 @@ SENTINEL = 0x5A5A5A5A5A5A5A5A                    # offsets canary
 @pytest.fixture(scope="module")
 def ctx():
     import circkit_amd
+    import torch
     c = circkit_amd.Context(0)
+    # torch's stream, not the ctx's own non-blocking one: the tests fill their canaried outputs with torch.full right before
+    # the call, and a fill still running on another stream lands on top of what the count kernel wrote (seen once at
+    # 8,388,608 records: offsets[0] and the total came back as canaries)
+    c.set_stream(torch.cuda.current_stream().cuda_stream)
     yield c
     c.close()
 
