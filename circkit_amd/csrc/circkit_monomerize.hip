@@ -11,13 +11,9 @@
 #include <string.h>
 
 #include "../../include/circkit.h"
+#include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
 #include "monomerize.h"
 
-// the ctx lives in circkit_hip.hip; this file sees it through these
-hipStream_t ck_ctx_stream(circkit_ctx* c);
-int ck_ctx_device(circkit_ctx* c);
-int ck_ctx_fail(circkit_ctx* c, int code, const char* msg);
-void** ck_ctx_monomerize_slot(circkit_ctx* c, void (*release)(void*));
 
 namespace {
 
@@ -42,16 +38,6 @@ struct MonoState {                   // host-buffer form staging (grow only)
     uint32_t* d_end = nullptr; uint64_t cap_end = 0;
 };
 
-#define CKM_HIP(c, call)                                                                            \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            char m_[256];                                                                           \
-            snprintf(m_, sizeof m_, "%s failed: %s", #call, hipGetErrorString(e_));               \
-            return ck_ctx_fail(c, e_ == hipErrorOutOfMemory ? CIRCKIT_ERR_OOM : CIRCKIT_ERR_HIP, m_); \
-        }                                                                                           \
-    } while (0)
-
 void release_state(void* p)
 {
     MonoState* S = (MonoState*)p;
@@ -63,7 +49,7 @@ void release_state(void* p)
 
 MonoState* state(circkit_ctx* c)
 {
-    void** slot = ck_ctx_monomerize_slot(c, release_state);
+    void** slot = ck_ctx_slot(c, CK_UNIT_MONOMERIZE, release_state);
     if (!*slot) *slot = new MonoState();
     return (MonoState*)*slot;
 }
@@ -73,7 +59,7 @@ int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
 {
     if (want <= *cap) return CIRCKIT_OK;
     if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CKM_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
+    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
     *cap = want;
     return CIRCKIT_OK;
 }
@@ -100,7 +86,7 @@ int launch(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, ui
     uint64_t grid = (n + MONO_WAVES - 1) / MONO_WAVES;
     if (grid > MONO_MAX_GRID) grid = MONO_MAX_GRID;
     hipLaunchKernelGGL(monomerize_kernel, dim3((uint32_t)grid), dim3(MONO_WG), 0, ck_ctx_stream(c), d_bytes, d_offsets, n, P, d_end);
-    CKM_HIP(c, hipGetLastError());
+    CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
 }
 
@@ -117,7 +103,7 @@ int circkit_monomerize_batch_device(circkit_ctx* c, const uint8_t* d_bytes, cons
     ck_mono::Params P;
     int rc = make_params(c, params, &P);
     if (rc) return rc;
-    CKM_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     return launch(c, d_bytes, d_offsets, n, P, d_end);
 }
 
@@ -136,18 +122,18 @@ int circkit_monomerize_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_
         if (offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_TOO_LONG, "a record of 2^32 symbols or more");
     }
     if (n == 0) return CIRCKIT_OK;
-    CKM_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     MonoState* S = state(c);
     const uint64_t nb = offsets[n];
     if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
     if ((rc = grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
     if ((rc = grow(c, &S->d_end, &S->cap_end, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (nb) CKM_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CKM_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
+    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if ((rc = launch(c, S->d_in, S->d_off, n, P, S->d_end))) return rc;
-    CKM_HIP(c, hipMemcpyAsync(end, S->d_end, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CKM_HIP(c, hipStreamSynchronize(st));
+    CK_HIP(c, hipMemcpyAsync(end, S->d_end, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
     return CIRCKIT_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "../../include/circkit.h"
+#include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
 #include "orfs.h"
 
 using ck_orfs::Orf;
@@ -21,11 +22,6 @@ using ck_orfs::Filter;
 
 static_assert(sizeof(Orf) == sizeof(circkit_orf), "device ORF layout");
 
-// the ctx lives in circkit_hip.hip; this file sees it through these
-hipStream_t ck_ctx_stream(circkit_ctx* c);
-int ck_ctx_device(circkit_ctx* c);
-int ck_ctx_fail(circkit_ctx* c, int code, const char* msg);
-void** ck_ctx_orfs_slot(circkit_ctx* c, void (*release)(void*));
 
 namespace {
 
@@ -156,16 +152,6 @@ struct OrfState {
     Orf* d_orfs = nullptr; uint64_t cap_orfs = 0;
 };
 
-#define CKO_HIP(c, call)                                                                            \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            char m_[256];                                                                           \
-            snprintf(m_, sizeof m_, "%s failed: %s", #call, hipGetErrorString(e_));               \
-            return ck_ctx_fail(c, e_ == hipErrorOutOfMemory ? CIRCKIT_ERR_OOM : CIRCKIT_ERR_HIP, m_); \
-        }                                                                                           \
-    } while (0)
-
 void release_state(void* p)
 {
     OrfState* S = (OrfState*)p;
@@ -178,7 +164,7 @@ void release_state(void* p)
 
 OrfState* state(circkit_ctx* c)
 {
-    void** slot = ck_ctx_orfs_slot(c, release_state);
+    void** slot = ck_ctx_slot(c, CK_UNIT_ORFS, release_state);
     if (!*slot) *slot = new OrfState();
     return (OrfState*)*slot;
 }
@@ -188,7 +174,7 @@ int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
 {
     if (want <= *cap) return CIRCKIT_OK;
     if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CKO_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
+    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
     *cap = want;
     return CIRCKIT_OK;
 }
@@ -226,7 +212,7 @@ int launch_count(circkit_ctx* c, OrfState* S, const uint8_t* d_bytes, const uint
     hipStream_t st = ck_ctx_stream(c);
     const uint64_t grid = n ? (n + ORF_WG - 1) / ORF_WG : 1;
     hipLaunchKernelGGL(orfs_count_kernel, dim3((uint32_t)grid), dim3(ORF_WG), 0, st, d_bytes, d_offsets, n, A, d_orf_offsets);
-    CKO_HIP(c, hipGetLastError());
+    CK_HIP(c, hipGetLastError());
     if (n == 0) return CIRCKIT_OK;
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     int rc = grow(c, &S->d_sums, &S->cap_sums, tiles);
@@ -234,7 +220,7 @@ int launch_count(circkit_ctx* c, OrfState* S, const uint8_t* d_bytes, const uint
     hipLaunchKernelGGL(scan_tile_sums, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_orf_offsets + 1, n, S->d_sums);
     hipLaunchKernelGGL(scan_sums, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles);
     hipLaunchKernelGGL(scan_apply, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, d_orf_offsets + 1, n, (const uint64_t*)S->d_sums);
-    CKO_HIP(c, hipGetLastError());
+    CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
 }
 
@@ -245,7 +231,7 @@ int launch_emit(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offset
     const uint64_t grid = (n + ORF_WG - 1) / ORF_WG;
     hipLaunchKernelGGL(orfs_emit_kernel, dim3((uint32_t)grid), dim3(ORF_WG), 0, ck_ctx_stream(c), d_bytes, d_offsets, n, A,
                        d_orf_offsets, d_orfs, capacity);
-    CKO_HIP(c, hipGetLastError());
+    CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
 }
 
@@ -262,14 +248,14 @@ int circkit_orfs_batch_device(circkit_ctx* c, const uint8_t* d_bytes, const uint
     OrfArgs A;
     int rc = make_args(c, params, &A);
     if (rc) return rc;
-    CKO_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     OrfState* S = state(c);
-    if (!S->h_total) CKO_HIP(c, hipHostMalloc((void**)&S->h_total, sizeof(uint64_t), hipHostMallocDefault));
+    if (!S->h_total) CK_HIP(c, hipHostMalloc((void**)&S->h_total, sizeof(uint64_t), hipHostMallocDefault));
     rc = launch_count(c, S, d_bytes, d_offsets, n, A, d_orf_offsets);
     if (rc) return rc;
     rc = launch_emit(c, d_bytes, d_offsets, n, A, d_orf_offsets, (Orf*)d_orfs, capacity);
     if (rc) return rc;
-    CKO_HIP(c, hipMemcpyAsync(S->h_total, d_orf_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
+    CK_HIP(c, hipMemcpyAsync(S->h_total, d_orf_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
     S->capacity = capacity;
     S->host_last = false;
     return CIRCKIT_OK;
@@ -279,7 +265,7 @@ int circkit_orfs_status(circkit_ctx* c, uint64_t* total)
 {
     if (!c) return CIRCKIT_ERR_INVALID_ARG;
     OrfState* S = state(c);
-    CKO_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t t = S->host_last ? S->host_total : S->h_total ? *S->h_total : 0;
     if (total) *total = t;
     if (t > S->capacity) {
@@ -299,18 +285,18 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     OrfArgs A;
     int rc = make_args(c, params, &A);
     if (rc) return rc;
-    CKO_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     OrfState* S = state(c);
     const uint64_t nb = offsets[n];
     if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
     if ((rc = grow(c, &S->d_off, &S->cap_rec, n + 1))) return rc;
     if ((rc = grow(c, &S->d_orf_off, &S->cap_orf_off, n + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (nb) CKO_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CKO_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
+    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if ((rc = launch_count(c, S, S->d_in, S->d_off, n, A, S->d_orf_off))) return rc;
-    CKO_HIP(c, hipMemcpyAsync(orf_offsets, S->d_orf_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CKO_HIP(c, hipStreamSynchronize(st));
+    CK_HIP(c, hipMemcpyAsync(orf_offsets, S->d_orf_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
     const uint64_t t = orf_offsets[n];
     if (total) *total = t;
     S->host_last = true; S->host_total = t; S->capacity = capacity;
@@ -322,8 +308,8 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     if (t == 0) return CIRCKIT_OK;
     if ((rc = grow(c, &S->d_orfs, &S->cap_orfs, t))) return rc;
     if ((rc = launch_emit(c, S->d_in, S->d_off, n, A, S->d_orf_off, S->d_orfs, t))) return rc;
-    CKO_HIP(c, hipMemcpyAsync(orfs, S->d_orfs, t * sizeof(Orf), hipMemcpyDeviceToHost, st));
-    CKO_HIP(c, hipStreamSynchronize(st));
+    CK_HIP(c, hipMemcpyAsync(orfs, S->d_orfs, t * sizeof(Orf), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
     return CIRCKIT_OK;
 }
 

@@ -485,3 +485,77 @@ def test_table_calls_after_a_resolve_are_refused(ctx):
         torch.cuda.synchronize()
         assert bool((t["out"] == SENT64).all())
         _answers_a_small_batch(ctx)
+
+
+# ---- 8. the table's state: one per ctx, and none of it borrowed ------------------------------------------------------------
+def test_table_state_is_per_ctx():
+    """Two ctxs on device 0, their calls interleaved one by one: the same 3000 keys go into both tables, with base_index 0 in A
+    and 1 000 000 in B, and each answers with its own indices.  Then A alone overflows (uniq_reset(1): 1024 slots, 3000 distinct
+    keys): A's status counts the 1976 keys that found no slot, B's stays clean and B's answers stay what they were -- the
+    table, its overflow counter and the rest of the uniq state belong to one ctx each.  B still answers after A is destroyed."""
+    import torch
+    import circkit_amd
+    n, base_b = 3000, 1_000_000
+    h = K.random_keys(np.random.default_rng(808), n)
+    i = np.arange(n, dtype=np.uint64)
+    a, b = circkit_amd.Context(0), circkit_amd.Context(0)
+    try:
+        for c in (a, b):
+            c.set_stream(torch.cuda.current_stream().cuda_stream)
+        d_h = _dev(h)
+        a.uniq_reset(4096)
+        b.uniq_reset(4096)
+        a.uniq_insert_device(d_h, n, 0)
+        b.uniq_insert_device(d_h, n, base_b)
+        got_a, got_b = _lookup(a, "device", h), _lookup(b, "device", h)
+        assert np.array_equal(got_a, i)
+        assert np.array_equal(got_b, i + np.uint64(base_b))
+        assert _status(a) == (0, 0) and _status(b) == (0, 0)
+
+        a.uniq_reset(1)
+        a.uniq_insert_device(d_h, n, 0)
+        answered = _lookup(a, "device", h) != EMPTY
+        assert int(answered.sum()) == 1024
+        assert _status(a) == (OOM, int((~answered).sum())) and int((~answered).sum()) == n - 1024
+        assert _status(b) == (0, 0)
+        assert np.array_equal(_lookup(b, "device", h), i + np.uint64(base_b))
+
+        a.close()
+        assert np.array_equal(_lookup(b, "device", h), i + np.uint64(base_b))
+        assert _status(b) == (0, 0)
+    finally:
+        a.close()
+        b.close()
+
+
+def test_the_host_form_owns_its_staging():
+    """circkit_uniq_first_seen between two host canonicalize batches on one ctx, with more keys (5000) than anything the ctx has
+    staged (8 records): the batch of 8 records of 64 bases gives the same bytes, hashes, indices and strands before and after --
+    those of the oracle -- and both first-seen arrays (5000 keys, half of them repeats; 500 more from base_index 5000, 100 of
+    them keys of the first batch) are the restatement over the joined stream."""
+    import circkit_amd
+    from oracle import oracle
+    rng = np.random.default_rng(909)
+    data = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=8 * 64)]
+    offsets = np.arange(9, dtype=np.uint64) * np.uint64(64)
+    exp_bytes, exp_hash = oracle.canonicalize_batch(data, offsets, want_bytes=True, want_hash=True)
+    pool = K.random_keys(rng, 2500 + 400)
+    h1 = rng.permutation(np.concatenate([pool[:2500], pool[:2500]]))
+    h2 = rng.permutation(np.concatenate([h1[rng.choice(5000, size=100, replace=False)], pool[2500:]]))
+    exp = K.expected_first_seen(np.concatenate([h1, h2]))
+    c = circkit_amd.Context(0)
+    try:
+        canon = lambda: c.canonicalize_batch(data, offsets, want_bytes=True, want_index=True, want_strand=True, want_xxh3=True)   # noqa: E731
+        first = canon()
+        fs1 = c.uniq_first_seen(h1, 0)
+        second = canon()
+        fs2 = c.uniq_first_seen(h2, 5000)
+        for out in (first, second):
+            assert np.array_equal(out["bytes"], exp_bytes)
+            assert np.array_equal(out["xxh3"], exp_hash)
+        assert np.array_equal(first["index"], second["index"]) and np.array_equal(first["strand"], second["strand"])
+        assert np.array_equal(fs1, exp[:5000].astype(np.uint64)), int((fs1 != exp[:5000]).sum())
+        assert np.array_equal(fs2, exp[5000:].astype(np.uint64)), int((fs2 != exp[5000:]).sum())
+        assert _status(c) == (0, 0)
+    finally:
+        c.close()

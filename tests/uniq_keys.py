@@ -1,7 +1,7 @@
 """Seeded key generators (NumPy only) that aim the uniq table's tests at the code random keys never reach, and the plain
 restatement of first-seen every such test compares against.
 
-The generators mirror two functions of circkit_amd/csrc/circkit_hip.hip -- only to AIM the input:
+The generators mirror two functions of circkit_amd/csrc/circkit_uniq.hip -- only to AIM the input:
   uniq_slot(h, mask) = (h ^ (h >> 29)) & mask        where a key starts probing (clustered)
   bkt_of(h, log2b)   = h >> (64 - log2b)             which LDS bucket a key of a bucketed resolve goes to (top_bits, bucket_shard)
 and one that is a contract written in include/circkit.h:

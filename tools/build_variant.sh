@@ -3,5 +3,6 @@
 set -e
 R=$(cd $(dirname $0)/.. && pwd)
 tag=$1; shift
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC "$@" -o $R/circkit_amd/libcirckit_hip_$tag.so \
-  $R/circkit_amd/csrc/circkit_hip.hip $R/circkit_amd/csrc/fasta_host.cpp
+# the library's sources: circkit_amd/build.py HIP_SOURCES, the one list
+srcs=$(cd $R && python3 -c "from circkit_amd.build import CSRC, HIP_SOURCES; print(' '.join(CSRC + '/' + s for s in HIP_SOURCES))")
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC "$@" -o $R/circkit_amd/libcirckit_hip_$tag.so $srcs

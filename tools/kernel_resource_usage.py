@@ -3,12 +3,16 @@
 python tools/kernel_resource_usage.py > profiles/r0N_kernel_resource_usage.txt"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "circkit_amd", "csrc", "circkit_hip.hip")
-r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/dev/null"],
-                   capture_output=True, text=True)
+sys.path.insert(0, root)
+from circkit_amd.build import CSRC, HIP_SOURCES       # the library's sources: one list
+remarks = []
+for src in HIP_SOURCES:
+    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage",
+                        os.path.join(CSRC, src), "-o", "/dev/null"], capture_output=True, text=True)
+    remarks += r.stderr.split("\n")
 cur = None
 rows = []
-for line in r.stderr.split("\n"):
+for line in remarks:
     m = re.search(r"remark: (.*?) \[-Rpass-analysis", line)
     if not m:
         continue
