@@ -6,6 +6,7 @@
     xxhash_rust::xxh3::xxh3_64               call site src/uniq.rs:45     -> xxh3_64(b)
     Monomerizer::last_monomer_end_index[_sensitive]  lib/src/monomerize.rs:97, :122  -> monomer_end_index(b, ...)
     Monomerizer::monomerize[_sensitive]      lib/src/monomerize.rs:138, :146 -> monomerize(b, ...)
+    the worker + writer closures             src/monomerize.rs:72-131        -> monomers_batch(data, offsets, ...)
 
 Everything computes on the GPU through libcirckit_hip.so; there is no CPU fallback -- importing works
 without a GPU (so the ABI can be inspected), creating a Context does not.
@@ -75,6 +76,9 @@ SIGNATURES = {
     "circkit_monomerize_batch_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "circkit_monomerize_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "circkit_monomer_end_index": (_i, [_vp, _vp, _sz, _vp, ctypes.POINTER(_sz), ctypes.POINTER(_i)]),
+    "circkit_monomers_compact_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "circkit_monomers_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "circkit_monomers_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -145,6 +149,25 @@ def monomerize_params(seed_len=10, max_mismatch=None, min_identity=None, sensiti
     p.min_identity = float(min_identity) if min_identity is not None else 0.0
     p.sensitive = int(bool(sensitive))
     return p
+
+
+# circkit_monomer_filter (include/circkit.h)
+class MonomerFilter(ctypes.Structure):
+    _fields_ = [("min_length", _u64), ("max_length", _u64), ("min_overlap", _u64), ("min_overlap_percent", ctypes.c_double),
+                ("use_min_overlap_percent", _u32), ("keep_all", _u32)]
+
+
+def monomer_filter(min_length=0, max_length=None, min_overlap=None, min_overlap_percent=None, keep_all=False):
+    """circkit_monomer_filter from Python values: the writer's options of `circkit monomerize` (src/monomerize.rs:94-131).
+    None = the option is not given."""
+    f = MonomerFilter()
+    f.min_length = int(min_length)
+    f.max_length = 2 ** 64 - 1 if max_length is None else int(max_length)
+    f.min_overlap = int(min_overlap or 0)
+    f.use_min_overlap_percent = int(min_overlap_percent is not None)
+    f.min_overlap_percent = float(min_overlap_percent) if min_overlap_percent is not None else 0.0
+    f.keep_all = int(bool(keep_all))
+    return f
 
 
 _lib = None
@@ -420,6 +443,46 @@ class Context:
                                                        ctypes.byref(p), _ptr(out)))
         return out[:n]
 
+    def monomers_compact_device(self, d_bytes, d_offsets, n_records, d_end, d_out_bytes, d_out_offsets, d_out_src, d_full_len=None,
+                                d_kept_end=None, filter=None, **kw):
+        """Enqueues circkit_monomers_compact_device: the writer's filters (monomer_filter keywords, or filter=) on the end
+        indices d_end, and the written monomers packed into the CSR batch d_out_bytes / d_out_offsets, with d_out_src[j] =
+        the input index of output record j.  monomers_status() waits and returns the totals."""
+        f = filter if filter is not None else monomer_filter(**kw)
+        self._check(self._lib.circkit_monomers_compact_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), _ptr(d_end),
+                                                              _ptr(d_full_len), ctypes.byref(f),
+                                                              _ptr(d_out_bytes), _ptr(d_out_offsets), _ptr(d_out_src), _ptr(d_kept_end)))
+
+    def monomers_status(self):
+        """Waits for the last compact; returns (number of written records, their bytes)."""
+        m, b = _u64(0), _u64(0)
+        self._check(self._lib.circkit_monomers_status(self._h, ctypes.byref(m), ctypes.byref(b)))
+        return m.value, b.value
+
+    def monomers_batch(self, data, offsets, full_len=None, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False, **filter):
+        """The monomers `circkit monomerize` writes for a host CSR batch of normalized records, as a CSR batch: (out_data,
+        out_offsets, out_src, kept_end).  out_src[j] = the input index of output record j; kept_end[i] = the end index of input
+        record i that survived the filters (monomer_filter keywords), MONOMER_NONE otherwise.  full_len: full_seq().len() per
+        record where it differs from the normalized length."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        p = monomerize_params(seed_len, max_mismatch, min_identity, sensitive)
+        f = monomer_filter(**filter)
+        fl = np.ascontiguousarray(full_len, dtype=np.uint64) if full_len is not None else None
+        if fl is not None and len(fl) != n:
+            raise ValueError("full_len must have one entry per record")
+        out = np.empty(max(len(data), 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        out_src = np.zeros(max(n, 1), dtype=np.uint64)
+        kept = np.full(max(n, 1), MONOMER_NONE, dtype=np.uint32)
+        m = _u64(0)
+        self._check(self._lib.circkit_monomers_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, ctypes.byref(p),
+                                                     ctypes.byref(f), _ptr(fl), _ptr(out), _ptr(out_off), _ptr(out_src), _ptr(kept),
+                                                     ctypes.byref(m)))
+        m = m.value
+        return out[:int(out_off[m])], out_off[:m + 1], out_src[:m], kept[:n]
+
     def monomer_end_index(self, s, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False):
         """lib/src/monomerize.rs:97 / :122 on any bytes: the end index, or None."""
         s = bytes(s)
@@ -512,6 +575,10 @@ def monomer_end_index(s, **kw):
 
 def monomerize(s, **kw):
     return default_context().monomerize(s, **kw)
+
+
+def monomers_batch(data, offsets, **kw):
+    return default_context().monomers_batch(data, offsets, **kw)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

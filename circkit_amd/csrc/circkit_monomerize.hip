@@ -5,6 +5,11 @@
 // global memory whatever its length (16-byte loads, contiguous across the wave); a 1 kb record is one scan step, a long one
 // is walked by the same wave step by step.  Records of 2^32 symbols or more are not processed (NONE); the host form refuses
 // the batch with CIRCKIT_ERR_TOO_LONG.
+//
+// Compact (the writer closure on the device, monomer_compact.h): compact_decide_kernel applies the writer's filters, one lane
+// per record; three scan kernels turn (written, written length) into each written record's slot and byte offset and the two
+// totals; compact_gather_kernel packs the monomers, by output bytes.  All five are enqueued back to back: the totals stay in
+// ctx-owned device memory, which is why the gather runs a fixed grid that strides over however many tiles there turn out to be.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -13,6 +18,7 @@
 #include "../../include/circkit.h"
 #include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
 #include "monomerize.h"
+#include "monomer_compact.h"
 
 
 namespace {
@@ -32,18 +38,165 @@ __global__ __launch_bounds__(MONO_WG) void monomerize_kernel(const uint8_t* __re
     }
 }
 
+
+// ---- compact: decide, scan, gather ------------------------------------------------------------------------------------
+constexpr int COMPACT_WG = 256;                       // decide: one lane per record
+constexpr int CSCAN_WG = 256, CSCAN_ITEMS = 8, CSCAN_TILE = CSCAN_WG * CSCAN_ITEMS;      // records per scan tile: 2048
+constexpr uint32_t COMPACT_MAX_GRID = 1u << 20;       // decide strides over the records beyond this many workgroups
+constexpr uint32_t GATHER_GRID = 2048;                // workgroups of the gather: 8 per CU, striding over the output tiles
+enum { T_RECORDS, T_BYTES, T_OVERLAP, T_WORDS };      // the totals of a compact, in device memory
+
+__global__ __launch_bounds__(COMPACT_WG) void compact_decide_kernel(const uint64_t* __restrict__ offsets, uint64_t n,
+                                                                    const uint32_t* __restrict__ end, const uint64_t* __restrict__ full_len,
+                                                                    ck_compact::Filter F, uint64_t* __restrict__ w, uint32_t* __restrict__ kept_end)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * COMPACT_WG;
+    for (uint64_t i = (uint64_t)blockIdx.x * COMPACT_WG + threadIdx.x; i < n; i += stride) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        uint32_t kept;
+        w[i] = ck_compact::decide(len, full_len ? full_len[i] : len, end[i], F, &kept);
+        if (kept_end) kept_end[i] = kept;
+    }
+}
+
+struct Pair { uint64_t cnt, bytes; };                 // written records, written bytes
+__device__ inline Pair pair_of(uint64_t w) { return Pair{ w >> 63, w & ~ck_compact::WRITTEN }; }
+
+// inclusive scan over the workgroup; *total = the workgroup's sum
+__device__ inline Pair block_scan(Pair v, Pair* lds, Pair* total)
+{
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    for (int d = 1; d < CSCAN_WG; d <<= 1) {
+        Pair add{ 0, 0 };
+        if (threadIdx.x >= (unsigned)d) add = lds[threadIdx.x - d];
+        __syncthreads();
+        lds[threadIdx.x].cnt += add.cnt;
+        lds[threadIdx.x].bytes += add.bytes;
+        __syncthreads();
+    }
+    const Pair r = lds[threadIdx.x];
+    *total = lds[CSCAN_WG - 1];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(CSCAN_WG) void compact_tile_sums_kernel(const uint64_t* __restrict__ w, uint64_t n, Pair* __restrict__ sums)
+{
+    __shared__ Pair lds[CSCAN_WG];
+    const uint64_t t0 = (uint64_t)blockIdx.x * CSCAN_TILE + (uint64_t)threadIdx.x * CSCAN_ITEMS;
+    Pair v{ 0, 0 }, total;
+    for (int k = 0; k < CSCAN_ITEMS; ++k)
+        if (t0 + k < n) { const Pair x = pair_of(w[t0 + k]); v.cnt += x.cnt; v.bytes += x.bytes; }
+    block_scan(v, lds, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// One workgroup: the tile sums become exclusive, CSCAN_WG of them at a time; then the totals, out_offsets[0], and the refusal of
+// an output buffer that overlaps the input payload (its owed room: as many bytes as the payload), after which nothing is written.
+__global__ __launch_bounds__(CSCAN_WG) void compact_scan_sums_kernel(Pair* __restrict__ sums, uint64_t n_tiles, const uint8_t* bytes,
+                                                                     const uint64_t* __restrict__ offsets, uint64_t n, const uint8_t* out,
+                                                                     uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ totals)
+{
+    __shared__ Pair lds[CSCAN_WG];
+    Pair carry{ 0, 0 };
+    for (uint64_t b = 0; b < n_tiles; b += CSCAN_WG) {
+        const uint64_t idx = b + threadIdx.x;
+        Pair v{ 0, 0 }, chunk;
+        if (idx < n_tiles) v = sums[idx];
+        const Pair inc = block_scan(v, lds, &chunk);
+        if (idx < n_tiles) sums[idx] = Pair{ carry.cnt + inc.cnt - v.cnt, carry.bytes + inc.bytes - v.bytes };
+        carry.cnt += chunk.cnt;
+        carry.bytes += chunk.bytes;
+    }
+    if (threadIdx.x == 0) {
+        bool overlap = false;
+        if (n) {
+            const uint64_t p0 = offsets[0], p1 = offsets[n];
+            const uintptr_t in_lo = (uintptr_t)bytes + p0, in_hi = (uintptr_t)bytes + p1, out_lo = (uintptr_t)out, out_hi = out_lo + (p1 - p0);
+            overlap = p1 > p0 && out_lo < in_hi && in_lo < out_hi;
+        }
+        totals[T_RECORDS] = overlap ? 0 : carry.cnt;
+        totals[T_BYTES] = overlap ? 0 : carry.bytes;
+        totals[T_OVERLAP] = overlap ? 1 : 0;
+        if (out_offsets) out_offsets[0] = 0;
+    }
+}
+
+// written record i goes to slot j: out_offsets[j + 1] = where it ends, out_src[j] = i, src_start[j] = where it starts in the input
+__global__ __launch_bounds__(CSCAN_WG) void compact_apply_kernel(const uint64_t* __restrict__ w, uint64_t n, const Pair* __restrict__ sums,
+                                                                 const uint64_t* __restrict__ totals, const uint64_t* __restrict__ offsets,
+                                                                 uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ out_src,
+                                                                 uint64_t* __restrict__ src_start)
+{
+    __shared__ Pair lds[CSCAN_WG];
+    if (totals[T_OVERLAP]) return;                    // the same for the whole grid
+    const uint64_t t0 = (uint64_t)blockIdx.x * CSCAN_TILE + (uint64_t)threadIdx.x * CSCAN_ITEMS;
+    uint64_t loc[CSCAN_ITEMS];
+    Pair v{ 0, 0 }, total;
+    for (int k = 0; k < CSCAN_ITEMS; ++k) {
+        loc[k] = t0 + k < n ? w[t0 + k] : 0;
+        const Pair x = pair_of(loc[k]);
+        v.cnt += x.cnt; v.bytes += x.bytes;
+    }
+    const Pair inc = block_scan(v, lds, &total);
+    const Pair base = sums[blockIdx.x];
+    uint64_t j = base.cnt + inc.cnt - v.cnt, at = base.bytes + inc.bytes - v.bytes;
+    for (int k = 0; k < CSCAN_ITEMS; ++k) {
+        if (!(loc[k] & ck_compact::WRITTEN)) continue;
+        at += loc[k] & ~ck_compact::WRITTEN;
+        out_offsets[j + 1] = at;
+        out_src[j] = t0 + k;
+        src_start[j] = offsets[t0 + k];
+        ++j;
+    }
+}
+
+__global__ __launch_bounds__(64 * ck_compact::GATHER_WAVES) void compact_gather_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets,
+                                                                                        uint64_t n, const uint64_t* __restrict__ out_offsets,
+                                                                                        const uint64_t* __restrict__ src_start,
+                                                                                        const uint64_t* __restrict__ totals, uint8_t* __restrict__ out)
+{
+    ck_compact::Gather G;
+    G.bytes = bytes;
+    G.p0 = offsets[0]; G.p1 = offsets[n];
+    G.out_offsets = out_offsets; G.src_start = src_start;
+    G.m = totals[T_RECORDS]; G.B = totals[T_BYTES];
+    G.out = out;
+    if (G.B == 0) return;
+    const uint64_t n_gran = (((uint64_t)(uintptr_t)out & 15u) + G.B + 15) / 16;
+    const uint64_t n_tiles = (n_gran + ck_compact::TILE_GRANULES - 1) / ck_compact::TILE_GRANULES;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_compact::gather_tile(G, t);
+}
+
 struct MonoState {                   // host-buffer form staging (grow only)
     uint8_t* d_in = nullptr; uint64_t cap_in = 0;
     uint64_t* d_off = nullptr; uint64_t cap_off = 0;
     uint32_t* d_end = nullptr; uint64_t cap_end = 0;
+    // compact: scan scratch, the totals on the device and their pinned copy
+    uint64_t* d_w = nullptr; uint64_t cap_w = 0;
+    Pair* d_sums = nullptr; uint64_t cap_sums = 0;
+    uint64_t* d_src_start = nullptr; uint64_t cap_src_start = 0;
+    uint64_t* d_totals = nullptr;
+    uint64_t* h_totals = nullptr;
+    bool host_last = false;          // the last compact was the host form: its totals are host_totals
+    uint64_t host_totals[T_WORDS] = { 0, 0, 0 };
+    // compact, host-buffer form staging
+    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
+    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
+    uint64_t* d_out_src = nullptr; uint64_t cap_out_src = 0;
+    uint32_t* d_kept = nullptr; uint64_t cap_kept = 0;
+    uint64_t* d_full = nullptr; uint64_t cap_full = 0;
 };
 
 void release_state(void* p)
 {
     MonoState* S = (MonoState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_in, S->d_off, S->d_end };
+    void* ptrs[] = { S->d_in, S->d_off, S->d_end, S->d_w, S->d_sums, S->d_src_start, S->d_totals, S->d_out, S->d_out_off, S->d_out_src,
+                     S->d_kept, S->d_full };
     for (void* q : ptrs) if (q) (void)hipFree(q);
+    if (S->h_totals) (void)hipHostFree(S->h_totals);
     delete S;
 }
 
@@ -87,6 +240,51 @@ int launch(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, ui
     if (grid > MONO_MAX_GRID) grid = MONO_MAX_GRID;
     hipLaunchKernelGGL(monomerize_kernel, dim3((uint32_t)grid), dim3(MONO_WG), 0, ck_ctx_stream(c), d_bytes, d_offsets, n, P, d_end);
     CK_HIP(c, hipGetLastError());
+    return CIRCKIT_OK;
+}
+
+// the five kernels of a compact and the copy of its totals, on the ctx stream; nothing waits
+int launch_compact(circkit_ctx* c, MonoState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint32_t* d_end,
+                   const uint64_t* d_full_len, const circkit_monomer_filter* f, uint8_t* d_out_bytes, uint64_t* d_out_offsets,
+                   uint64_t* d_out_src, uint32_t* d_kept_end)
+{
+    ck_compact::Filter F;
+    F.min_length = f->min_length; F.max_length = f->max_length; F.min_overlap = f->min_overlap;
+    F.min_overlap_percent = f->min_overlap_percent;
+    F.use_percent = f->use_min_overlap_percent ? 1 : 0;
+    F.keep_all = f->keep_all ? 1 : 0;
+    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
+    if (!S->h_totals) CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
+    int rc;
+    if ((rc = grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
+    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (n) {
+        uint64_t grid = (n + COMPACT_WG - 1) / COMPACT_WG;
+        if (grid > COMPACT_MAX_GRID) grid = COMPACT_MAX_GRID;
+        hipLaunchKernelGGL(compact_decide_kernel, dim3((uint32_t)grid), dim3(COMPACT_WG), 0, st, d_offsets, n, d_end, d_full_len, F, S->d_w,
+                           d_kept_end);
+        hipLaunchKernelGGL(compact_tile_sums_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, S->d_sums);
+    }
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(CSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, n,
+                       (const uint8_t*)d_out_bytes, d_out_offsets, S->d_totals);
+    if (n) {
+        hipLaunchKernelGGL(compact_apply_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, (const Pair*)S->d_sums,
+                           (const uint64_t*)S->d_totals, d_offsets, d_out_offsets, d_out_src, S->d_src_start);
+        hipLaunchKernelGGL(compact_gather_kernel, dim3(GATHER_GRID), dim3(64 * ck_compact::GATHER_WAVES), 0, st, d_bytes, d_offsets, n,
+                           (const uint64_t*)d_out_offsets, (const uint64_t*)S->d_src_start, (const uint64_t*)S->d_totals, d_out_bytes);
+    }
+    CK_HIP(c, hipGetLastError());
+    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    S->host_last = false;
+    return CIRCKIT_OK;
+}
+
+int check_totals(circkit_ctx* c, const uint64_t* t)
+{
+    if (t[T_OVERLAP]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_bytes overlaps the input payload: nothing was written");
     return CIRCKIT_OK;
 }
 
@@ -148,6 +346,85 @@ int circkit_monomer_end_index(circkit_ctx* c, const uint8_t* s, size_t n, const 
     if (rc) return rc;
     if (found) *found = e != CIRCKIT_MONOMER_NONE;
     if (end) *end = e != CIRCKIT_MONOMER_NONE ? (size_t)e : n;
+    return CIRCKIT_OK;
+}
+
+int circkit_monomers_compact_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint32_t* d_end,
+                                    const uint64_t* d_full_len, const circkit_monomer_filter* filter, uint8_t* d_out_bytes,
+                                    uint64_t* d_out_offsets, uint64_t* d_out_src, uint32_t* d_kept_end)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (!filter) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null filter");
+    if (n && (!d_bytes || !d_offsets || !d_end || !d_out_bytes || !d_out_offsets || !d_out_src))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    return launch_compact(c, state(c), d_bytes, d_offsets, n, d_end, d_full_len, filter, d_out_bytes, d_out_offsets, d_out_src, d_kept_end);
+}
+
+int circkit_monomers_status(circkit_ctx* c, uint64_t* n_kept, uint64_t* kept_bytes)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    MonoState* S = state(c);
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    const uint64_t none[T_WORDS] = { 0, 0, 0 };
+    const uint64_t* t = S->host_last ? S->host_totals : S->h_totals ? S->h_totals : none;
+    if (n_kept) *n_kept = t[T_RECORDS];
+    if (kept_bytes) *kept_bytes = t[T_BYTES];
+    return check_totals(c, t);
+}
+
+int circkit_monomers_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, const circkit_monomerize_params* params,
+                           const circkit_monomer_filter* filter, const uint64_t* full_len, uint8_t* out_bytes, uint64_t* out_offsets,
+                           uint64_t* out_src, uint32_t* kept_end, uint64_t* n_kept)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (!filter) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null filter");
+    if (!offsets || !out_offsets || (n && (!out_src || (offsets[n] > offsets[0] && (!bytes || !out_bytes)))))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
+    if (n >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
+    ck_mono::Params P;
+    int rc = make_params(c, params, &P);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+        if (offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_TOO_LONG, "a record of 2^32 symbols or more");
+    }
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    MonoState* S = state(c);
+    out_offsets[0] = 0;
+    if (n_kept) *n_kept = 0;
+    S->host_last = true;
+    S->host_totals[T_RECORDS] = S->host_totals[T_BYTES] = S->host_totals[T_OVERLAP] = 0;
+    if (n == 0) return CIRCKIT_OK;
+    const uint64_t nb = offsets[n];
+    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
+    if ((rc = grow(c, &S->d_end, &S->cap_end, n))) return rc;
+    if ((rc = grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
+    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
+    if ((rc = grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
+    if ((rc = grow(c, &S->d_kept, &S->cap_kept, n))) return rc;
+    if (full_len && (rc = grow(c, &S->d_full, &S->cap_full, n))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
+    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (full_len) CK_HIP(c, hipMemcpyAsync(S->d_full, full_len, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if ((rc = launch(c, S->d_in, S->d_off, n, P, S->d_end))) return rc;
+    if ((rc = launch_compact(c, S, S->d_in, S->d_off, n, S->d_end, full_len ? S->d_full : nullptr, filter, S->d_out, S->d_out_off,
+                             S->d_out_src, S->d_kept))) return rc;
+    CK_HIP(c, hipStreamSynchronize(st));
+    S->host_last = true;
+    for (int k = 0; k < T_WORDS; ++k) S->host_totals[k] = S->h_totals[k];
+    if ((rc = check_totals(c, S->host_totals))) return rc;
+    const uint64_t m = S->host_totals[T_RECORDS], B = S->host_totals[T_BYTES];
+    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (m) CK_HIP(c, hipMemcpyAsync(out_src, S->d_out_src, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (kept_end) CK_HIP(c, hipMemcpyAsync(kept_end, S->d_kept, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (B) CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
+    if (n_kept) *n_kept = m;
     return CIRCKIT_OK;
 }
 

@@ -298,6 +298,53 @@ int circkit_monomerize_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint6
 int circkit_monomer_end_index(circkit_ctx* ctx, const uint8_t* s, size_t n, const circkit_monomerize_params* params,
                               size_t* end, int* found);
 
+/* The writer's filters (src/monomerize.rs:94-131; `--min-length`, `--max-length`, `--min-overlap`,
+ * `--min-overlap-percent`, `-k` of src/commands.rs).  For a record of n symbols whose full_seq() holds f >= n bytes and
+ * whose end index is idx:
+ *   min_length / max_length   idx < min_length or idx > max_length: None (:97-103)
+ *   min_overlap               f - idx < min_overlap: None (:106-112)
+ *   min_overlap_percent       used iff use_min_overlap_percent: (f - idx) as f64 / idx as f64 < it: None (:115-125); one
+ *                             IEEE division, so idx = 0 gives inf or NaN and a NaN threshold never rejects
+ *   keep_all                  a record whose index is None is written whole instead of being dropped (:130-131) */
+typedef struct circkit_monomer_filter {
+    uint64_t min_length;            /* --min-length, 0 = none */
+    uint64_t max_length;            /* --max-length, UINT64_MAX = none */
+    uint64_t min_overlap;           /* --min-overlap, 0 = none */
+    double   min_overlap_percent;   /* --min-overlap-percent, used iff use_min_overlap_percent */
+    uint32_t use_min_overlap_percent;
+    uint32_t keep_all;              /* -k */
+} circkit_monomer_filter;
+
+/* Replaces, for a whole batch, the writer closure of src/monomerize.rs:90-131 and the slicing `&full_seq[..end_idx]` (:135):
+ * decides per record what the reference would write and packs the written monomers back to back into a new CSR batch,
+ * which circkit_canonicalize_batch_device / circkit_uniq_* take as it is.  Device pointers; the call only enqueues work on
+ * the ctx stream.
+ *   d_end          the end indices of circkit_monomerize_batch_device; CIRCKIT_MONOMER_NONE or anything beyond its record:
+ *                  None.  The worker's pre-check (:80) needs no step of its own: monomerize returns indices in
+ *                  [seed_len, n - seed_len] only, so a record shorter than --min-length fails min_length.
+ *   d_full_len     uint64[n_records] full_seq().len() per record (>= its normalized length), or null: the normalized length
+ *   d_out_bytes    room for offsets[n_records] - offsets[0] bytes; must not overlap the input payload
+ *   d_out_offsets  uint64[n_records + 1]: entries 0..m are written, d_out_offsets[0] = 0; m = the number of written records
+ *   d_out_src      uint64[n_records]: entries 0..m-1 are written, the input index of output record j
+ *   d_kept_end     uint32[n_records] or null: the index that survived the filters, or CIRCKIT_MONOMER_NONE
+ * A record is written with its first idx bytes, or, under keep_all and without an index, whole.  offsets[0] need not be 0;
+ * no pointer needs any alignment.  Null filter, or a null required buffer with n_records > 0: INVALID_ARG.  Whether the
+ * output overlaps the payload depends on offsets that only the device holds: the device checks it before anything is
+ * packed, writes no record, and circkit_monomers_status reports INVALID_ARG. */
+int circkit_monomers_compact_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                    const uint32_t* d_end, const uint64_t* d_full_len, const circkit_monomer_filter* filter,
+                                    uint8_t* d_out_bytes, uint64_t* d_out_offsets, uint64_t* d_out_src, uint32_t* d_kept_end);
+/* Waits for the most recent compact of this ctx (device or host form): *n_kept = its m, *kept_bytes = d_out_offsets[m].
+ * CIRCKIT_ERR_INVALID_ARG when that compact refused its output buffer (see above); both totals are 0 then. */
+int circkit_monomers_status(circkit_ctx* ctx, uint64_t* n_kept, uint64_t* kept_bytes);
+/* src/monomerize.rs:85-131 with HOST buffers: circkit_monomerize_batch_device and the compact on one stream; synchronizes.
+ * offsets[0] must be 0; a record of 2^32 symbols or more: CIRCKIT_ERR_TOO_LONG and nothing is computed.  Copied back:
+ * out_offsets[0..m], out_src[0..m), kept_end (when given) and out_offsets[m] bytes of out_bytes; *n_kept = m. */
+int circkit_monomers_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                           const circkit_monomerize_params* params, const circkit_monomer_filter* filter,
+                           const uint64_t* full_len, uint8_t* out_bytes, uint64_t* out_offsets, uint64_t* out_src,
+                           uint32_t* kept_end, uint64_t* n_kept);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
