@@ -6,7 +6,7 @@ monomerize.py  `circkit monomerize` over the GPU batch call (also `python -m cir
            callable: circkit_amd.monomerize(s, ...) is Monomerizer::monomerize on one record
 """
 from .api import (CirckitError, Context, canonicalize, default_context, find_orfs, lmsr, lmsr_index, load_library,  # noqa: F401
-                  monomer_end_index, monomer_filter, monomerize_params, monomers_batch, normalize, orf_params, xxh3_64)
+                  monomer_end_index, monomer_filter, monomerize_params, monomers_batch, normalize, orf_params, uniq_batch, xxh3_64)
 from . import uniq  # noqa: F401,E402
 
 

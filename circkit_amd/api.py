@@ -7,6 +7,7 @@
     Monomerizer::last_monomer_end_index[_sensitive]  lib/src/monomerize.rs:97, :122  -> monomer_end_index(b, ...)
     Monomerizer::monomerize[_sensitive]      lib/src/monomerize.rs:138, :146 -> monomerize(b, ...)
     the worker + writer closures             src/monomerize.rs:72-131        -> monomers_batch(data, offsets, ...)
+    one shard of `circkit uniq`              src/uniq.rs:27-66               -> uniq_batch(data, offsets, ...)
 
 Everything computes on the GPU through libcirckit_hip.so; there is no CPU fallback -- importing works
 without a GPU (so the ABI can be inspected), creating a Context does not.
@@ -58,6 +59,9 @@ SIGNATURES = {
     "circkit_uniq_status": (_i, [_vp, ctypes.POINTER(_u32)]),
     "circkit_uniq_resolve_device": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "circkit_uniq_first_seen": (_i, [_vp, _vp, _u64, _u64, _vp]),
+    "circkit_uniq_compact_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "circkit_uniq_compact_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "circkit_uniq_batch": (_i, [_vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64)]),
     "circkit_fasta_parse": (_i, [_vp, _sz, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "circkit_fasta_error": (ctypes.c_char_p, [_vp]),
     "circkit_fasta_n_records": (_u64, [_vp]),
@@ -355,6 +359,39 @@ class Context:
             self._check(rc)
         return n.value
 
+    def uniq_compact_device(self, d_bytes, d_offsets, n_records, d_first_seen, d_out_bytes, d_out_offsets, d_out_src, base_index=0,
+                            d_dup_src=None, d_dup_first=None):
+        """Enqueues circkit_uniq_compact_device: the records with d_first_seen[i] == base_index + i packed into the CSR batch
+        d_out_bytes / d_out_offsets, d_out_src[j] = the input index of output record j; the others listed in d_dup_src (their
+        input index) and d_dup_first (their d_first_seen, a global index), each where given.  uniq_compact_status() waits and
+        returns the totals; uniq_status() says whether the table behind d_first_seen took every key."""
+        self._check(self._lib.circkit_uniq_compact_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), _ptr(d_first_seen),
+                                                          int(base_index), _ptr(d_out_bytes), _ptr(d_out_offsets), _ptr(d_out_src),
+                                                          _ptr(d_dup_src), _ptr(d_dup_first)))
+
+    def uniq_compact_status(self):
+        """Waits for the last uniq compact; returns (number of kept records, their bytes)."""
+        m, b = _u64(0), _u64(0)
+        self._check(self._lib.circkit_uniq_compact_status(self._h, ctypes.byref(m), ctypes.byref(b)))
+        return m.value, b.value
+
+    def uniq_batch(self, data, offsets, canonicalize=False):
+        """What `circkit uniq` (`-c` with canonicalize=True) writes for a host CSR batch of normalized records, as a CSR batch:
+        (out_data, out_offsets, out_src, first_seen).  out_src[j] = the input index of output record j; first_seen[i] = the
+        index of the first record with record i's canonical hash: record i is a duplicate of it where that is not i."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.empty(max(len(data), 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        out_src = np.zeros(max(n, 1), dtype=np.uint64)
+        fs = np.zeros(max(n, 1), dtype=np.uint64)
+        m = _u64(0)
+        self._check(self._lib.circkit_uniq_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, int(bool(canonicalize)),
+                                                 _ptr(out), _ptr(out_off), _ptr(out_src), _ptr(fs), ctypes.byref(m)))
+        m = m.value
+        return out[:int(out_off[m])], out_off[:m + 1], out_src[:m], fs[:n]
+
     # -- host batches (numpy) -------------------------------------------------------------------
     def canonicalize_batch(self, data, offsets, want_bytes=True, want_index=False, want_strand=False,
                            want_xxh3=False):
@@ -579,6 +616,10 @@ def monomerize(s, **kw):
 
 def monomers_batch(data, offsets, **kw):
     return default_context().monomers_batch(data, offsets, **kw)
+
+
+def uniq_batch(data, offsets, **kw):
+    return default_context().uniq_batch(data, offsets, **kw)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

@@ -10,6 +10,8 @@
 // per record; three scan kernels turn (written, written length) into each written record's slot and byte offset and the two
 // totals; compact_gather_kernel packs the monomers, by output bytes.  All five are enqueued back to back: the totals stay in
 // ctx-owned device memory, which is why the gather runs a fixed grid that strides over however many tiles there turn out to be.
+// Everything behind the decide kernel knows a record only by its word w[i], and is open to the other units through
+// ck_compact_launch.h: circkit_uniq_compact.hip fills w from uniq's first_seen and has the dropped records listed as well.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -17,6 +19,7 @@
 
 #include "../../include/circkit.h"
 #include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
+#include "ck_compact_launch.h"
 #include "monomerize.h"
 #include "monomer_compact.h"
 
@@ -44,7 +47,7 @@ constexpr int COMPACT_WG = 256;                       // decide: one lane per re
 constexpr int CSCAN_WG = 256, CSCAN_ITEMS = 8, CSCAN_TILE = CSCAN_WG * CSCAN_ITEMS;      // records per scan tile: 2048
 constexpr uint32_t COMPACT_MAX_GRID = 1u << 20;       // decide strides over the records beyond this many workgroups
 constexpr uint32_t GATHER_GRID = 2048;                // workgroups of the gather: 8 per CU, striding over the output tiles
-enum { T_RECORDS, T_BYTES, T_OVERLAP, T_WORDS };      // the totals of a compact, in device memory
+enum { T_RECORDS = CK_COMPACT_RECORDS, T_BYTES = CK_COMPACT_BYTES, T_OVERLAP = CK_COMPACT_OVERLAP, T_WORDS = CK_COMPACT_WORDS };      // the totals of a compact, in device memory
 
 __global__ __launch_bounds__(COMPACT_WG) void compact_decide_kernel(const uint64_t* __restrict__ offsets, uint64_t n,
                                                                     const uint32_t* __restrict__ end, const uint64_t* __restrict__ full_len,
@@ -123,11 +126,14 @@ __global__ __launch_bounds__(CSCAN_WG) void compact_scan_sums_kernel(Pair* __res
     }
 }
 
-// written record i goes to slot j: out_offsets[j + 1] = where it ends, out_src[j] = i, src_start[j] = where it starts in the input
+// written record i goes to slot j: out_offsets[j + 1] = where it ends, out_src[j] = i, src_start[j] = where it starts in the input.
+// A dropped record i goes to slot i - (the written records before it) of the dropped list, which the running j already is:
+// dup_src[slot] = i, dup_first[slot] = dup_val[i], each where the pointer is given.
 __global__ __launch_bounds__(CSCAN_WG) void compact_apply_kernel(const uint64_t* __restrict__ w, uint64_t n, const Pair* __restrict__ sums,
                                                                  const uint64_t* __restrict__ totals, const uint64_t* __restrict__ offsets,
                                                                  uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ out_src,
-                                                                 uint64_t* __restrict__ src_start)
+                                                                 uint64_t* __restrict__ src_start, uint64_t* __restrict__ dup_src,
+                                                                 uint64_t* __restrict__ dup_first, const uint64_t* __restrict__ dup_val)
 {
     __shared__ Pair lds[CSCAN_WG];
     if (totals[T_OVERLAP]) return;                    // the same for the whole grid
@@ -143,7 +149,14 @@ __global__ __launch_bounds__(CSCAN_WG) void compact_apply_kernel(const uint64_t*
     const Pair base = sums[blockIdx.x];
     uint64_t j = base.cnt + inc.cnt - v.cnt, at = base.bytes + inc.bytes - v.bytes;
     for (int k = 0; k < CSCAN_ITEMS; ++k) {
-        if (!(loc[k] & ck_compact::WRITTEN)) continue;
+        if (!(loc[k] & ck_compact::WRITTEN)) {
+            if (t0 + k < n) {
+                const uint64_t slot = t0 + k - j;
+                if (dup_src) dup_src[slot] = t0 + k;
+                if (dup_first) dup_first[slot] = dup_val[t0 + k];
+            }
+            continue;
+        }
         at += loc[k] & ~ck_compact::WRITTEN;
         out_offsets[j + 1] = at;
         out_src[j] = t0 + k;
@@ -177,8 +190,7 @@ struct MonoState {                   // host-buffer form staging (grow only)
     uint64_t* d_w = nullptr; uint64_t cap_w = 0;
     Pair* d_sums = nullptr; uint64_t cap_sums = 0;
     uint64_t* d_src_start = nullptr; uint64_t cap_src_start = 0;
-    uint64_t* d_totals = nullptr;
-    uint64_t* h_totals = nullptr;
+    ck_compact_totals totals;
     bool host_last = false;          // the last compact was the host form: its totals are host_totals
     uint64_t host_totals[T_WORDS] = { 0, 0, 0 };
     // compact, host-buffer form staging
@@ -193,10 +205,9 @@ void release_state(void* p)
 {
     MonoState* S = (MonoState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_in, S->d_off, S->d_end, S->d_w, S->d_sums, S->d_src_start, S->d_totals, S->d_out, S->d_out_off, S->d_out_src,
-                     S->d_kept, S->d_full };
+    void* ptrs[] = { S->d_in, S->d_off, S->d_end, S->d_w, S->d_sums, S->d_src_start, S->d_out, S->d_out_off, S->d_out_src, S->d_kept, S->d_full };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    ck_compact_totals_release(&S->totals);
     delete S;
 }
 
@@ -253,31 +264,16 @@ int launch_compact(circkit_ctx* c, MonoState* S, const uint8_t* d_bytes, const u
     F.min_overlap_percent = f->min_overlap_percent;
     F.use_percent = f->use_min_overlap_percent ? 1 : 0;
     F.keep_all = f->keep_all ? 1 : 0;
-    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
-    if (!S->h_totals) CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
-    const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
+    uint64_t* d_w;
     int rc;
-    if ((rc = grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
-    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
-    if ((rc = grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
+    if ((rc = ck_compact_reserve(c, n, &d_w))) return rc;
     if (n) {
         uint64_t grid = (n + COMPACT_WG - 1) / COMPACT_WG;
         if (grid > COMPACT_MAX_GRID) grid = COMPACT_MAX_GRID;
-        hipLaunchKernelGGL(compact_decide_kernel, dim3((uint32_t)grid), dim3(COMPACT_WG), 0, st, d_offsets, n, d_end, d_full_len, F, S->d_w,
-                           d_kept_end);
-        hipLaunchKernelGGL(compact_tile_sums_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, S->d_sums);
+        hipLaunchKernelGGL(compact_decide_kernel, dim3((uint32_t)grid), dim3(COMPACT_WG), 0, ck_ctx_stream(c), d_offsets, n, d_end, d_full_len, F,
+                           d_w, d_kept_end);
     }
-    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(CSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, n,
-                       (const uint8_t*)d_out_bytes, d_out_offsets, S->d_totals);
-    if (n) {
-        hipLaunchKernelGGL(compact_apply_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, (const Pair*)S->d_sums,
-                           (const uint64_t*)S->d_totals, d_offsets, d_out_offsets, d_out_src, S->d_src_start);
-        hipLaunchKernelGGL(compact_gather_kernel, dim3(GATHER_GRID), dim3(64 * ck_compact::GATHER_WAVES), 0, st, d_bytes, d_offsets, n,
-                           (const uint64_t*)d_out_offsets, (const uint64_t*)S->d_src_start, (const uint64_t*)S->d_totals, d_out_bytes);
-    }
-    CK_HIP(c, hipGetLastError());
-    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = ck_compact_launch(c, &S->totals, d_bytes, d_offsets, n, d_out_bytes, d_out_offsets, d_out_src, nullptr, nullptr, nullptr))) return rc;
     S->host_last = false;
     return CIRCKIT_OK;
 }
@@ -289,6 +285,49 @@ int check_totals(circkit_ctx* c, const uint64_t* t)
 }
 
 }  // namespace
+
+// ---- ck_compact_launch.h: the scan, apply and gather for whoever filled w ----------------------------------------------------
+void ck_compact_totals_release(ck_compact_totals* T)
+{
+    if (T->d) (void)hipFree(T->d);
+    if (T->h) (void)hipHostFree(T->h);
+    T->d = T->h = nullptr;
+}
+
+int ck_compact_reserve(circkit_ctx* c, uint64_t n, uint64_t** d_w)
+{
+    MonoState* S = state(c);
+    const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
+    int rc;
+    if ((rc = grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
+    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
+    *d_w = S->d_w;
+    return CIRCKIT_OK;
+}
+
+int ck_compact_launch(circkit_ctx* c, ck_compact_totals* T, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+                      uint8_t* d_out_bytes, uint64_t* d_out_offsets, uint64_t* d_out_src, uint64_t* d_dup_src, uint64_t* d_dup_first,
+                      const uint64_t* d_dup_val)
+{
+    MonoState* S = state(c);                          // (sized by ck_compact_reserve for this n)
+    if (!T->d) CK_HIP(c, hipMalloc((void**)&T->d, T_WORDS * sizeof(uint64_t)));
+    if (!T->h) CK_HIP(c, hipHostMalloc((void**)&T->h, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
+    hipStream_t st = ck_ctx_stream(c);
+    if (n) hipLaunchKernelGGL(compact_tile_sums_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, S->d_sums);
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(CSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, n,
+                       (const uint8_t*)d_out_bytes, d_out_offsets, T->d);
+    if (n) {
+        hipLaunchKernelGGL(compact_apply_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, (const Pair*)S->d_sums,
+                           (const uint64_t*)T->d, d_offsets, d_out_offsets, d_out_src, S->d_src_start, d_dup_src, d_dup_first, d_dup_val);
+        hipLaunchKernelGGL(compact_gather_kernel, dim3(GATHER_GRID), dim3(64 * ck_compact::GATHER_WAVES), 0, st, d_bytes, d_offsets, n,
+                           (const uint64_t*)d_out_offsets, (const uint64_t*)S->d_src_start, (const uint64_t*)T->d, d_out_bytes);
+    }
+    CK_HIP(c, hipGetLastError());
+    CK_HIP(c, hipMemcpyAsync(T->h, T->d, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    return CIRCKIT_OK;
+}
 
 extern "C" {
 
@@ -368,7 +407,7 @@ int circkit_monomers_status(circkit_ctx* c, uint64_t* n_kept, uint64_t* kept_byt
     MonoState* S = state(c);
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t none[T_WORDS] = { 0, 0, 0 };
-    const uint64_t* t = S->host_last ? S->host_totals : S->h_totals ? S->h_totals : none;
+    const uint64_t* t = S->host_last ? S->host_totals : S->totals.h ? S->totals.h : none;
     if (n_kept) *n_kept = t[T_RECORDS];
     if (kept_bytes) *kept_bytes = t[T_BYTES];
     return check_totals(c, t);
@@ -416,7 +455,7 @@ int circkit_monomers_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
                              S->d_out_src, S->d_kept))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     S->host_last = true;
-    for (int k = 0; k < T_WORDS; ++k) S->host_totals[k] = S->h_totals[k];
+    for (int k = 0; k < T_WORDS; ++k) S->host_totals[k] = S->totals.h[k];
     if ((rc = check_totals(c, S->host_totals))) return rc;
     const uint64_t m = S->host_totals[T_RECORDS], B = S->host_totals[T_BYTES];
     CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));

@@ -1,5 +1,6 @@
 // monomer_compact.h -- the writer closure of `circkit monomerize` for a device batch (the reference's src/monomerize.rs:94-131):
 // decide() applies the writer's filters to one record's end index; gather_tile() packs the written monomers back to back.
+// decide_uniq() is `circkit uniq`'s writer decision (src/uniq.rs:47-66) in the same form, for the same gather.
 // Written against wave_prims.h only; every collective (ballot) sits in wave-uniform control flow, so the CPU fiber harness of
 // tests/emu/ runs this source unchanged.
 //
@@ -54,6 +55,14 @@ CK_DEV uint64_t decide(uint64_t n, uint64_t full, uint32_t e, const Filter& F, u
     *kept = some ? e : NONE;
     if (some) return WRITTEN | idx;
     return F.keep_all ? WRITTEN | n : 0;
+}
+
+// The same word for `circkit uniq` (src/uniq.rs:47-66: "emit the record, or write a table row"): record i of a batch whose
+// record 0 has global index base is emitted, whole, iff it is the first with its hash: first_seen == base + i.  Any other
+// value drops it, ~0 (the answer for a key that found no slot in the table) included.
+CK_DEV uint64_t decide_uniq(uint64_t n, uint64_t first_seen, uint64_t base, uint64_t i)
+{
+    return first_seen == base + i ? WRITTEN | n : 0;
 }
 
 // ---- 64-way search, wave-uniform: the j in [0, m) with a[j] <= p < a[j + 1]; a[0] <= p < a[m] ----

@@ -194,6 +194,46 @@ int circkit_uniq_status(circkit_ctx* ctx, uint32_t* n_overflowed);
 int circkit_uniq_first_seen(circkit_ctx* ctx, const uint64_t* hash, uint64_t n, uint64_t base_index,
                             uint64_t* first_seen);
 
+/* Replaces, for a whole batch, the writer side of src/uniq.rs:47-66 ("emit the record, or write a table row"): packs the
+ * records that are the first with their hash back to back into a new CSR batch, which circkit_orfs_batch_device /
+ * circkit_canonicalize_batch_device take as it is, and lists the others with their first occurrence -- the (id, duplicate_id)
+ * rows of `--table`, as indices.  Device pointers; the call only enqueues work on the ctx stream.
+ *   d_bytes        the payload to pack: the canonical bytes (`uniq -c`, :54-56) or the input's (:57-59); the call does not care
+ *   d_first_seen   uint64[n_records], what circkit_uniq_resolve_device, circkit_uniq_lookup_device (streaming batches) or
+ *                  circkit_uniq_gather_device (multi-GPU) wrote.  Record i is kept iff d_first_seen[i] == base_index + i; ANY
+ *                  other value drops it, ~0 included.  ~0 is the answer for a key that found no slot in an overflowed table:
+ *                  the caller owes a circkit_uniq_status before it trusts what was dropped.
+ *   base_index     the global index of record 0 of this batch, as in the call that produced d_first_seen
+ *   d_out_bytes    room for offsets[n_records] - offsets[0] bytes; must not overlap the input payload
+ *   d_out_offsets  uint64[n_records + 1]: entries 0..m are written, d_out_offsets[0] = 0; m = the number of kept records
+ *   d_out_src      uint64[n_records]: entries 0..m-1 are written, the input index of output record j, ascending
+ *   d_dup_src      uint64[n_records] or null: entry k = the input index of dropped record number k, in input order (:67)
+ *   d_dup_first    uint64[n_records] or null: entry k = that record's d_first_seen, a GLOBAL index: the first occurrence may
+ *                  belong to an earlier batch (:66).  Entries 0..n_records-m-1 of the two are written, nothing beyond.
+ * A zero-length record is a record: kept, it takes an entry of d_out_offsets and no bytes.  offsets[0] need not be 0; no
+ * pointer needs any alignment.  A null required buffer with n_records > 0: INVALID_ARG; with n_records == 0, d_out_offsets[0]
+ * = 0 is still written when that pointer is given.  Whether the output overlaps the payload depends on offsets that only the
+ * device holds: the device checks it before anything is packed, writes no record and no index (d_out_offsets[0] = 0 aside),
+ * and circkit_uniq_compact_status reports INVALID_ARG. */
+int circkit_uniq_compact_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                const uint64_t* d_first_seen, uint64_t base_index,
+                                uint8_t* d_out_bytes, uint64_t* d_out_offsets, uint64_t* d_out_src,
+                                uint64_t* d_dup_src, uint64_t* d_dup_first);
+/* Waits for the most recent uniq compact of this ctx (device or host form): *n_kept = its m, *kept_bytes = d_out_offsets[m].
+ * CIRCKIT_ERR_INVALID_ARG when that compact refused its output buffer (see above); both totals are 0 then.  The totals are
+ * this call's own: circkit_monomers_status keeps answering for the most recent monomer compact, and the other way round. */
+int circkit_uniq_compact_status(circkit_ctx* ctx, uint64_t* n_kept, uint64_t* kept_bytes);
+/* One shard of src/uniq.rs:27-66 with HOST buffers, on one stream: copy in, circkit_canonicalize_batch_device (the XXH3, and
+ * the canonical bytes only when canonical_out), circkit_uniq_resolve_device with base 0, the compact of the canonical bytes
+ * (canonical_out) or of the input, copy home; synchronizes.  Copied back: out_offsets[0..m], out_src[0..m), out_offsets[m]
+ * bytes of out_bytes and, when given, first_seen[0..n_records) -- what the host writes the table rows from; *n_kept = m.
+ * offsets[0] must be 0; n_records < 2^32 - 1 (resolve's limit; circkit_canonicalize_batch_device's own applies too).  A record
+ * that the canonicalize batch leaves unprocessed (circkit_ctx_batch_status): CIRCKIT_ERR_TOO_LONG and nothing is returned; a
+ * table overflow: the status of circkit_uniq_status.  The staging on the device is the ctx's and only grows.  As after
+ * circkit_uniq_resolve_device, the ctx table is private to the call until the next circkit_uniq_reset. */
+int circkit_uniq_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records, int canonical_out,
+                       uint8_t* out_bytes, uint64_t* out_offsets, uint64_t* out_src, uint64_t* first_seen, uint64_t* n_kept);
+
 /* ---- circular ORFs (`circkit orfs`) --------------------------------------------------------------- */
 /* One ORF as lib/src/orfs.rs:6-15 defines it (pub struct Orf), plus the strand it was found on.  start and stop are
  * positions on that strand (a reverse-strand ORF counts on revcomp(record), as the reference's RC list does);
