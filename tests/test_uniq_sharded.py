@@ -1,6 +1,10 @@
 """world_size-2 gloo test (CPU) of the multi-GPU uniq merge: shard -> all-gather hash sets -> first-seen.
 The GPU hash table is replaced by the CPU checker's first-seen routine (test infrastructure) so the
-exchange / global-index logic of circkit_amd/uniq.py runs without a GPU."""
+exchange / global-index logic of circkit_amd/uniq.py runs without a GPU.
+
+The same branches also run on the DEVICE kernels at world 2, 3 and 8 (unequal and empty shards, the bench's job-wide check) in
+tests/test_uniq_exchange_world_gpu.py, through the in-process world of tests/loopback_dist.py; tests/test_loopback_dist_cpu.py
+runs that file's shard shapes through the same loopback with the tables below."""
 import os
 import socket
 
