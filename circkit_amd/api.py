@@ -83,12 +83,20 @@ SIGNATURES = {
     "circkit_monomers_compact_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "circkit_monomers_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "circkit_monomers_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64)]),
+    "circkit_windows_gather_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "circkit_windows_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "circkit_windows_of_records_device": (_i, [_vp, _vp, _u64, _u32, ctypes.c_int64, ctypes.c_double, _vp]),
+    "circkit_orfs_windows_device": (_i, [_vp, _vp, _vp, _u64, _u64, _i, _vp]),
+    "circkit_windows_gather": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
 # circkit_orf / circkit_orf_params (include/circkit.h)
 ORF_NO_STOP = 0xFFFFFFFF
 ORF_DTYPE = np.dtype([("length", "<u8"), ("start", "<u4"), ("stop", "<u4"), ("wraps", "<u4"), ("strand", "<u4")])
+# circkit_window (include/circkit.h)
+WINDOW_DTYPE = np.dtype([("length", "<u8"), ("record", "<u4"), ("start", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
+WINDOW_KINDS = {"rotate_bases": 0, "rotate_percent": 1, "cat": 2, "decat": 3, "revcomp": 4}
 
 
 class OrfParams(ctypes.Structure):
@@ -460,6 +468,139 @@ class Context:
             return [(int(o["start"]), None if int(o["stop"]) == ORF_NO_STOP else int(o["stop"]), int(o["wraps"]), int(o["length"]))
                     for o in out[:cnt.value]]
 
+    # -- cyclic windows ------------------------------------------------------------------------
+    def windows_gather_device(self, d_bytes, d_offsets, n_records, d_windows, n_windows, d_out_bytes, out_capacity, d_out_offsets):
+        """Enqueues circkit_windows_gather_device: window k of d_windows (WINDOW_DTYPE, device) packed into
+        d_out_bytes[d_out_offsets[k] .. d_out_offsets[k + 1]).  windows_status() waits and returns the totals."""
+        self._check(self._lib.circkit_windows_gather_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), _ptr(d_windows),
+                                                            int(n_windows), _ptr(d_out_bytes), int(out_capacity), _ptr(d_out_offsets)))
+
+    def windows_status(self):
+        """Waits for the last windows gather; returns (total bytes, invalid windows).  Raises CirckitError: OOM when the total
+        exceeded the capacity, INVALID_ARG when the output overlapped the payload or windows were invalid."""
+        t, bad = _u64(0), _u64(0)
+        self._check(self._lib.circkit_windows_status(self._h, ctypes.byref(t), ctypes.byref(bad)))
+        return t.value, bad.value
+
+    def windows_of_records_device(self, d_offsets, n_records, kind, d_windows, bases=0, percent=0.0):
+        """Enqueues circkit_windows_of_records_device: one window per record into d_windows (WINDOW_DTYPE, device).  kind: a key
+        of WINDOW_KINDS or its number; bases / percent are read by the two rotate kinds only."""
+        k = WINDOW_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self._check(self._lib.circkit_windows_of_records_device(self._h, _ptr(d_offsets), int(n_records), k, int(bases), float(percent),
+                                                                _ptr(d_windows)))
+
+    def orfs_windows_device(self, d_orf_offsets, d_orfs, n_records, n_orfs, d_windows, include_stop=False):
+        """Enqueues circkit_orfs_windows_device: one window per ORF of an orfs_batch_device result into d_windows."""
+        self._check(self._lib.circkit_orfs_windows_device(self._h, _ptr(d_orf_offsets), _ptr(d_orfs), int(n_records), int(n_orfs),
+                                                          int(bool(include_stop)), _ptr(d_windows)))
+
+    def windows_gather(self, data, offsets, windows):
+        """The windows' bytes of a host CSR batch, packed: (out_bytes, out_offsets).  windows: an array of WINDOW_DTYPE.  Grows
+        its buffer to the reported total and runs again, as orfs_batch does; invalid windows raise CirckitError."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        windows = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+        n, m = len(offsets) - 1, len(windows)
+        out_off = np.zeros(m + 1, dtype=np.uint64)
+        cap = max(len(data), 1)
+        while True:
+            out = np.empty(cap, dtype=np.uint8)
+            total = _u64(0)
+            rc = self._lib.circkit_windows_gather(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(windows) if m else None,
+                                                  m, _ptr(out), cap, _ptr(out_off), ctypes.byref(total))
+            if rc == -5 and cap < total.value < 2 ** 64 - 1:      # grow to the reported total and run again
+                cap = total.value
+                continue
+            self._check(rc)
+            return out[:total.value], out_off
+
+    def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
+        """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
+        import torch
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, nb = len(offsets) - 1, int(offsets[-1]) - int(offsets[0])
+        dev = torch.device("cuda", self.device)
+        cap = {"cat": 2 * nb, "decat": nb // 2}.get(kind, nb)
+        with torch.cuda.device(dev):
+            # (records without a payload byte still want a pointer: one byte that no window reads)
+            d_bytes = torch.from_numpy(data).to(dev) if len(data) else torch.zeros(1, dtype=torch.uint8, device=dev)
+            d_offs = torch.from_numpy(offsets.view(np.int64)).to(dev)
+            torch.cuda.current_stream().synchronize()         # the copies are torch's, the kernels the ctx stream's
+            d_win = torch.empty(max(n, 1) * WINDOW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            d_out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            self.windows_of_records_device(d_offs, n, kind, d_win, bases=bases, percent=percent)
+            self.windows_gather_device(d_bytes, d_offs, n, d_win, n, d_out, cap, d_out_off)
+            total, _ = self.windows_status()
+            return d_out[:total].cpu().numpy(), d_out_off.cpu().numpy().view(np.uint64)
+
+    def rotate_batch(self, data, offsets, bases=None, percent=None):
+        """`circkit rotate --bases` / `--percent` on every record of a host CSR batch (src/rotate.rs:20-43): (bytes, offsets)."""
+        if (bases is None) == (percent is None):
+            raise ValueError("Must provide either bases or percent")
+        if percent is not None:
+            return self._records_windows(data, offsets, "rotate_percent", percent=percent)
+        if not -2 ** 63 <= int(bases) < 2 ** 63:
+            raise ValueError("bases must fit an i64")
+        return self._records_windows(data, offsets, "rotate_bases", bases=bases)
+
+    def cat_batch(self, data, offsets):
+        """`circkit cat`: every record twice in a row (src/concatenate.rs:10-32)."""
+        return self._records_windows(data, offsets, "cat")
+
+    def decat_batch(self, data, offsets):
+        """`circkit decat`: the first half of every record (src/concatenate.rs:34-54)."""
+        return self._records_windows(data, offsets, "decat")
+
+    def revcomp_batch(self, data, offsets):
+        """The reverse complement of every record (bio 1.3.1's dna complement, as canonicalize uses it)."""
+        return self._records_windows(data, offsets, "revcomp")
+
+    def orf_sequences(self, data, offsets, include_stop=False, **orf_kw):
+        """The ORFs of a host CSR batch of normalized records and their sequences, as `circkit orfs` writes them (`--include-stop`:
+        include_stop): (orf_offsets, orfs, seq_bytes, seq_offsets) with orfs an array of ORF_DTYPE and ORF k's sequence
+        seq_bytes[seq_offsets[k] .. seq_offsets[k + 1]).  One copy in; the ORF batch, the windows and the gather on the device;
+        then the copy home.  Keywords as orf_params."""
+        import torch
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        p = orf_params(**orf_kw)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d_bytes = torch.from_numpy(data).to(dev) if len(data) else torch.zeros(1, dtype=torch.uint8, device=dev)
+            d_offs = torch.from_numpy(offsets.view(np.int64)).to(dev)
+            torch.cuda.current_stream().synchronize()         # the copies are torch's, the kernels the ctx stream's
+            d_orf_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            cap = max(n, 1) * 4
+            while True:
+                d_orfs = torch.empty(cap * ORF_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                self.orfs_batch_device(d_bytes, d_offs, n, d_orf_off, d_orfs, cap, params=p)
+                t = _u64(0)
+                rc = self._lib.circkit_orfs_status(self._h, ctypes.byref(t))
+                if rc == -5 and t.value > cap:                    # grow to the reported total and run again
+                    cap = t.value
+                    continue
+                self._check(rc)
+                break
+            n_orfs = t.value
+            d_win = torch.empty(max(n_orfs, 1) * WINDOW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            d_seq_off = torch.empty(n_orfs + 1, dtype=torch.int64, device=dev)
+            self.orfs_windows_device(d_orf_off, d_orfs, n, n_orfs, d_win, include_stop=include_stop)
+            # the offsets first (a gather without room reports the total), then the gather into a buffer of that size
+            self.windows_gather_device(d_bytes, d_offs, n, d_win, n_orfs, None, 0, d_seq_off)
+            total = _u64(0)
+            rc = self._lib.circkit_windows_status(self._h, ctypes.byref(total), None)
+            if rc != -5:
+                self._check(rc)
+            d_seq = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+            if total.value:
+                self.windows_gather_device(d_bytes, d_offs, n, d_win, n_orfs, d_seq, total.value, d_seq_off)
+                self.windows_status()
+            orfs = d_orfs.cpu().numpy().view(ORF_DTYPE)[:n_orfs].copy()
+            return (d_orf_off.cpu().numpy().view(np.uint64), orfs, d_seq[:total.value].cpu().numpy(), d_seq_off.cpu().numpy().view(np.uint64))
+
     # -- monomerize -----------------------------------------------------------------------------
     def monomerize_batch_device(self, d_bytes, d_offsets, n_records, d_end, params=None, **kw):
         """Enqueues circkit_monomerize_batch_device: d_end (uint32[n_records], device) gets every record's end index or
@@ -620,6 +761,26 @@ def monomers_batch(data, offsets, **kw):
 
 def uniq_batch(data, offsets, **kw):
     return default_context().uniq_batch(data, offsets, **kw)
+
+
+def rotate_batch(data, offsets, bases=None, percent=None):
+    return default_context().rotate_batch(data, offsets, bases=bases, percent=percent)
+
+
+def cat_batch(data, offsets):
+    return default_context().cat_batch(data, offsets)
+
+
+def decat_batch(data, offsets):
+    return default_context().decat_batch(data, offsets)
+
+
+def revcomp_batch(data, offsets):
+    return default_context().revcomp_batch(data, offsets)
+
+
+def orf_sequences(data, offsets, include_stop=False, **orf_params):
+    return default_context().orf_sequences(data, offsets, include_stop=include_stop, **orf_params)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

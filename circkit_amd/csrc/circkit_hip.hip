@@ -837,6 +837,7 @@ struct circkit_ctx {
 // the other units' view of the ctx (ck_ctx.h)
 hipStream_t ck_ctx_stream(circkit_ctx* c) { return c->stream; }
 int ck_ctx_device(circkit_ctx* c) { return c->device; }
+const uint8_t* ck_ctx_complement(circkit_ctx* c) { return c->d_comp; }
 void** ck_ctx_slot(circkit_ctx* c, ck_unit unit, void (*release)(void*)) { c->units[unit].release = release; return &c->units[unit].p; }
 int ck_fail(circkit_ctx* c, int code, const char* fmt, ...)
 {

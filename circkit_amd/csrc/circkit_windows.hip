@@ -1,0 +1,381 @@
+// circkit_windows.hip -- cyclic windows of a device batch: the windows section of include/circkit.h.
+//
+// A gather is five steps on the ctx stream, nothing waits:
+//   windows_lengths_kernel     one lane per window: out_offsets[k + 1] = the bytes window k writes (window_gather.h
+//                              effective_length: 0 for an invalid window and on an empty record), invalid windows counted
+//   windows_tile_sums_kernel   the sum of each tile of WSCAN_TILE lengths
+//   windows_scan_sums_kernel   one workgroup: the tile sums become exclusive; then the total, its comparison with the
+//                              capacity and the refusal of an output that overlaps the payload
+//   windows_apply_kernel       out_offsets in place: the lengths become the offsets
+//   windows_gather_kernel      window_gather.h gather_tile over the output tiles, unless the scan refused the gather
+// The sums saturate (window_gather.h sat_add), so out_offsets never decreases whatever lengths the windows name.  The totals
+// stay in device memory and are copied to pinned memory behind the gather: circkit_windows_status waits and reads them.
+// windows_of_records_kernel and orfs_windows_kernel write the window lists of rotate / cat / decat / revcomp and of an ORF
+// batch from what the device already holds.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/circkit.h"
+#include "ck_ctx.h"
+#include "window_gather.h"
+
+using ck_windows::Window;
+
+static_assert(sizeof(Window) == sizeof(circkit_window) && sizeof(Window) == 24, "device window layout");
+static_assert((int)ck_windows::KIND_ROTATE_BASES == CIRCKIT_WINDOWS_ROTATE_BASES && (int)ck_windows::KIND_ROTATE_PERCENT == CIRCKIT_WINDOWS_ROTATE_PERCENT &&
+              (int)ck_windows::KIND_CAT == CIRCKIT_WINDOWS_CAT && (int)ck_windows::KIND_DECAT == CIRCKIT_WINDOWS_DECAT &&
+              (int)ck_windows::KIND_REVCOMP == CIRCKIT_WINDOWS_REVCOMP, "window kinds");
+
+namespace {
+
+constexpr int WIN_WG = 256;                            // lengths, of_records, orfs_windows: one lane per item
+constexpr int WSCAN_WG = 256, WSCAN_ITEMS = 8, WSCAN_TILE = WSCAN_WG * WSCAN_ITEMS;      // windows per scan tile: 2048
+constexpr uint32_t WIN_MAX_GRID = 1u << 20;            // the lanes stride over the items beyond this many workgroups
+constexpr uint32_t GATHER_GRID = 2048;                 // workgroups of the gather: 8 per CU, striding over the output tiles
+enum { T_TOTAL, T_INVALID, T_REFUSED, T_WORDS };       // the totals of a gather, in device memory
+enum { REFUSED_CAPACITY = 1, REFUSED_OVERLAP = 2 };
+
+__global__ __launch_bounds__(WIN_WG) void windows_lengths_kernel(const uint64_t* __restrict__ offsets, uint64_t n_records,
+                                                                 const Window* __restrict__ windows, uint64_t m,
+                                                                 uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ totals)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * WIN_WG;
+    for (uint64_t k = (uint64_t)blockIdx.x * WIN_WG + threadIdx.x; k < m; k += stride) {
+        bool invalid;
+        out_offsets[k + 1] = ck_windows::effective_length(windows[k], offsets, n_records, &invalid);
+        if (invalid) atomicAdd((unsigned long long*)&totals[T_INVALID], 1ull);
+    }
+}
+
+// exclusive scan over the workgroup, saturating; *total = the workgroup's sum
+__device__ inline uint64_t block_scan(uint64_t v, uint64_t* lds, uint64_t* total)
+{
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    for (int d = 1; d < WSCAN_WG; d <<= 1) {
+        const uint64_t add = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
+        __syncthreads();
+        lds[threadIdx.x] = ck_windows::sat_add(lds[threadIdx.x], add);
+        __syncthreads();
+    }
+    const uint64_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0;
+    *total = lds[WSCAN_WG - 1];
+    __syncthreads();
+    return before;
+}
+
+__global__ __launch_bounds__(WSCAN_WG) void windows_tile_sums_kernel(const uint64_t* __restrict__ len, uint64_t m, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t lds[WSCAN_WG];
+    const uint64_t t0 = (uint64_t)blockIdx.x * WSCAN_TILE + (uint64_t)threadIdx.x * WSCAN_ITEMS;
+    uint64_t v = 0, total;
+    for (int k = 0; k < WSCAN_ITEMS; ++k) if (t0 + k < m) v = ck_windows::sat_add(v, len[t0 + k]);
+    block_scan(v, lds, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// One workgroup: the tile sums become exclusive, WSCAN_WG of them at a time; then the total, out_offsets[0], and the two
+// refusals: a total beyond the capacity, and an output [out, out + total) that overlaps the input payload.
+__global__ __launch_bounds__(WSCAN_WG) void windows_scan_sums_kernel(uint64_t* __restrict__ sums, uint64_t n_tiles, const uint8_t* bytes,
+                                                                     const uint64_t* __restrict__ offsets, uint64_t n_records, const uint8_t* out,
+                                                                     uint64_t capacity, uint64_t* __restrict__ out_offsets,
+                                                                     uint64_t* __restrict__ totals)
+{
+    __shared__ uint64_t lds[WSCAN_WG];
+    uint64_t carry = 0;
+    for (uint64_t b = 0; b < n_tiles; b += WSCAN_WG) {
+        const uint64_t idx = b + threadIdx.x;
+        uint64_t chunk;
+        const uint64_t before = block_scan(idx < n_tiles ? sums[idx] : 0, lds, &chunk);
+        if (idx < n_tiles) sums[idx] = ck_windows::sat_add(carry, before);
+        carry = ck_windows::sat_add(carry, chunk);
+    }
+    if (threadIdx.x == 0) {
+        const uint64_t total = carry;
+        uint64_t refused = total > capacity || total == ~0ull ? REFUSED_CAPACITY : 0;
+        if (!refused && total && out && n_records) {
+            const uint64_t p0 = offsets[0], p1 = offsets[n_records];
+            const uintptr_t in_lo = (uintptr_t)bytes + p0, in_hi = (uintptr_t)bytes + p1, out_lo = (uintptr_t)out, out_hi = out_lo + total;
+            if (p1 > p0 && out_lo < in_hi && in_lo < out_hi) refused = REFUSED_OVERLAP;
+        }
+        totals[T_TOTAL] = total;
+        totals[T_REFUSED] = refused;
+        if (out_offsets) out_offsets[0] = 0;
+    }
+}
+
+// out_offsets[k + 1]: window k's length becomes where it ends
+__global__ __launch_bounds__(WSCAN_WG) void windows_apply_kernel(uint64_t* __restrict__ ends, uint64_t m, const uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t lds[WSCAN_WG];
+    const uint64_t t0 = (uint64_t)blockIdx.x * WSCAN_TILE + (uint64_t)threadIdx.x * WSCAN_ITEMS;
+    uint64_t loc[WSCAN_ITEMS];
+    uint64_t v = 0, total;
+    for (int k = 0; k < WSCAN_ITEMS; ++k) { loc[k] = t0 + k < m ? ends[t0 + k] : 0; v = ck_windows::sat_add(v, loc[k]); }
+    uint64_t run = ck_windows::sat_add(sums[blockIdx.x], block_scan(v, lds, &total));
+    for (int k = 0; k < WSCAN_ITEMS; ++k) {
+        run = ck_windows::sat_add(run, loc[k]);
+        if (t0 + k < m) ends[t0 + k] = run;
+    }
+}
+
+__global__ __launch_bounds__(64 * ck_windows::GATHER_WAVES) void windows_gather_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets,
+                                                                                        uint64_t n_records, const Window* __restrict__ windows, uint64_t m,
+                                                                                        const uint64_t* __restrict__ out_offsets,
+                                                                                        const uint64_t* __restrict__ totals, const uint8_t* __restrict__ comp,
+                                                                                        uint8_t* __restrict__ out)
+{
+    __shared__ uint8_t comp_lds[256];
+    for (uint32_t k = threadIdx.x; k < 256; k += 64 * ck_windows::GATHER_WAVES) comp_lds[k] = comp[k];
+    __syncthreads();
+    if (totals[T_REFUSED]) return;                    // the same for the whole grid
+    ck_windows::Gather G;
+    G.bytes = bytes; G.offsets = offsets;
+    G.p0 = offsets[0]; G.p1 = offsets[n_records];
+    G.windows = windows; G.out_offsets = out_offsets;
+    G.m = m; G.B = totals[T_TOTAL];
+    G.comp = comp_lds;
+    G.out = out;
+    if (G.B == 0) return;
+    const uint64_t n_gran = (((uint64_t)(uintptr_t)out & 15u) + G.B + 15) / 16;
+    const uint64_t n_tiles = (n_gran + ck_windows::TILE_GRANULES - 1) / ck_windows::TILE_GRANULES;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_windows::gather_tile(G, t);
+}
+
+__global__ __launch_bounds__(WIN_WG) void windows_of_records_kernel(const uint64_t* __restrict__ offsets, uint64_t n, uint32_t kind, int64_t bases,
+                                                                    double percent, Window* __restrict__ windows)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * WIN_WG;
+    for (uint64_t i = (uint64_t)blockIdx.x * WIN_WG + threadIdx.x; i < n; i += stride)
+        windows[i] = ck_windows::window_of_record(offsets[i + 1] - offsets[i], (uint32_t)i, kind, bases, percent);
+}
+
+// ORF k lies in the record r with orf_offsets[r] <= k < orf_offsets[r + 1]; an ORF that no record's range holds (offsets that
+// do not cover the list) gets a record beyond the batch: an invalid window
+__global__ __launch_bounds__(WIN_WG) void orfs_windows_kernel(const uint64_t* __restrict__ orf_offsets, const circkit_orf* __restrict__ orfs,
+                                                              uint64_t n_records, uint64_t n_orfs, uint32_t cut, Window* __restrict__ windows)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * WIN_WG;
+    for (uint64_t k = (uint64_t)blockIdx.x * WIN_WG + threadIdx.x; k < n_orfs; k += stride) {
+        uint64_t lo = 0, hi = n_records + 1;                   // the first entry beyond k is in (lo, hi]; entry n_records + 1 = infinity
+        if (orf_offsets[0] > k) hi = 0;
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (orf_offsets[mid] <= k) lo = mid; else hi = mid;
+        }
+        const circkit_orf o = orfs[k];
+        Window W;
+        W.length = o.length > cut ? o.length - cut : 0;
+        W.record = hi == 0 || lo >= n_records ? 0xFFFFFFFFu : (uint32_t)lo;
+        W.start = o.start;
+        W.strand = o.strand;
+        W.reserved = 0;
+        windows[k] = W;
+    }
+}
+
+struct WindowsState {
+    uint64_t* d_totals = nullptr;    // [T_WORDS] of the most recent gather, device
+    uint64_t* h_totals = nullptr;    // the same, page-locked host memory: valid once the ctx stream has run past the copy
+    uint64_t capacity = 0;           // of the most recent gather, for the status message
+    bool any = false;
+    uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
+    // circkit_windows_gather's staging (grow only)
+    uint8_t* d_in = nullptr; uint64_t cap_in = 0;
+    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
+    Window* d_win = nullptr; uint64_t cap_win = 0;
+    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
+    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
+};
+
+void release_state(void* p)
+{
+    WindowsState* S = (WindowsState*)p;
+    if (!S) return;
+    void* ptrs[] = { S->d_totals, S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    delete S;
+}
+
+WindowsState* state(circkit_ctx* c)
+{
+    void** slot = ck_ctx_slot(c, CK_UNIT_WINDOWS, release_state);
+    if (!*slot) *slot = new WindowsState();
+    return (WindowsState*)*slot;
+}
+
+template <typename T>
+int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
+{
+    if (want <= *cap) return CIRCKIT_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
+    *cap = want;
+    return CIRCKIT_OK;
+}
+
+uint32_t lane_grid(uint64_t items)
+{
+    const uint64_t grid = (items + WIN_WG - 1) / WIN_WG;
+    return (uint32_t)(grid > WIN_MAX_GRID ? WIN_MAX_GRID : grid);
+}
+
+// lengths, the scan with its refusals, and the copy of the totals: out_offsets is complete and S->h_totals valid once the stream
+// has run past it.  d_out is only compared with the payload.
+int launch_offsets(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                   const Window* d_windows, uint64_t m, const uint8_t* d_out, uint64_t capacity, uint64_t* d_out_offsets)
+{
+    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
+    if (!S->h_totals) CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    const uint64_t tiles = (m + WSCAN_TILE - 1) / WSCAN_TILE;
+    int rc;
+    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    if (m) {
+        hipLaunchKernelGGL(windows_lengths_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, S->d_totals);
+        hipLaunchKernelGGL(windows_tile_sums_kernel, dim3((uint32_t)tiles), dim3(WSCAN_WG), 0, st, (const uint64_t*)d_out_offsets + 1, m, S->d_sums);
+    }
+    hipLaunchKernelGGL(windows_scan_sums_kernel, dim3(1), dim3(WSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, m ? n_records : 0, d_out, capacity,
+                       d_out_offsets, S->d_totals);
+    if (m) hipLaunchKernelGGL(windows_apply_kernel, dim3((uint32_t)tiles), dim3(WSCAN_WG), 0, st, d_out_offsets + 1, m, (const uint64_t*)S->d_sums);
+    CK_HIP(c, hipGetLastError());
+    S->capacity = capacity;
+    S->any = true;
+    return CIRCKIT_OK;
+}
+
+int launch_gather(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records, const Window* d_windows,
+                  uint64_t m, const uint64_t* d_out_offsets, uint8_t* d_out)
+{
+    if (!m || !n_records) return CIRCKIT_OK;           // no window writes a byte
+    hipLaunchKernelGGL(windows_gather_kernel, dim3(GATHER_GRID), dim3(64 * ck_windows::GATHER_WAVES), 0, ck_ctx_stream(c), d_bytes, d_offsets, n_records,
+                       d_windows, m, d_out_offsets, (const uint64_t*)S->d_totals, ck_ctx_complement(c), d_out);
+    CK_HIP(c, hipGetLastError());
+    return CIRCKIT_OK;
+}
+
+int copy_totals(circkit_ctx* c, WindowsState* S)
+{
+    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
+    return CIRCKIT_OK;
+}
+
+// the verdict on totals the stream has delivered
+int check_totals(circkit_ctx* c, const uint64_t* t, uint64_t capacity)
+{
+    if (t[T_REFUSED] == REFUSED_CAPACITY)
+        return ck_fail(c, CIRCKIT_ERR_OOM, "the windows write %llu bytes, the buffer holds %llu: nothing was written", (unsigned long long)t[T_TOTAL],
+                       (unsigned long long)capacity);
+    if (t[T_REFUSED]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_bytes overlaps the input payload: nothing was written");
+    if (t[T_INVALID]) return ck_fail(c, CIRCKIT_ERR_INVALID_ARG, "%llu invalid windows were written as empty ones", (unsigned long long)t[T_INVALID]);
+    return CIRCKIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int circkit_windows_gather_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                  const circkit_window* d_windows, uint64_t n_windows, uint8_t* d_out_bytes, uint64_t out_capacity,
+                                  uint64_t* d_out_offsets)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (n_windows && (!d_windows || !d_out_offsets || (out_capacity && !d_out_bytes))) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows && n_records && (!d_bytes || !d_offsets)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    WindowsState* S = state(c);
+    int rc;
+    if ((rc = launch_offsets(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_bytes, out_capacity, d_out_offsets))) return rc;
+    if ((rc = launch_gather(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_offsets, d_out_bytes))) return rc;
+    return copy_totals(c, S);
+}
+
+int circkit_windows_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* n_invalid)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    WindowsState* S = state(c);
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    const uint64_t none[T_WORDS] = { 0, 0, 0 };
+    const uint64_t* t = S->any ? S->h_totals : none;
+    if (total_bytes) *total_bytes = t[T_TOTAL];
+    if (n_invalid) *n_invalid = t[T_INVALID];
+    return check_totals(c, t, S->capacity);
+}
+
+int circkit_windows_of_records_device(circkit_ctx* c, const uint64_t* d_offsets, uint64_t n_records, uint32_t kind, int64_t bases, double percent,
+                                      circkit_window* d_windows)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (kind >= (uint32_t)ck_windows::N_KINDS) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "unknown kind of window");
+    if ((kind == CIRCKIT_WINDOWS_ROTATE_BASES && bases == 0) || (kind == CIRCKIT_WINDOWS_ROTATE_PERCENT && percent == 0.0))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "Rotation by 0 is not allowed");       // src/rotate.rs:20-22
+    if (n_records && (!d_offsets || !d_windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "a window names its record in 32 bits: n_records must be <= 2^32 - 1");
+    if (!n_records) return CIRCKIT_OK;
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    hipLaunchKernelGGL(windows_of_records_kernel, dim3(lane_grid(n_records)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_offsets, n_records, kind, bases, percent,
+                       (Window*)d_windows);
+    CK_HIP(c, hipGetLastError());
+    return CIRCKIT_OK;
+}
+
+int circkit_orfs_windows_device(circkit_ctx* c, const uint64_t* d_orf_offsets, const circkit_orf* d_orfs, uint64_t n_records, uint64_t n_orfs,
+                                int include_stop, circkit_window* d_windows)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (n_orfs && (!d_orf_offsets || !d_orfs || !d_windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "a window names its record in 32 bits: n_records must be <= 2^32 - 1");
+    if (n_orfs >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_orfs too large");
+    if (!n_orfs) return CIRCKIT_OK;
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    hipLaunchKernelGGL(orfs_windows_kernel, dim3(lane_grid(n_orfs)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_orf_offsets, d_orfs, n_records, n_orfs,
+                       include_stop ? 0u : 3u, (Window*)d_windows);
+    CK_HIP(c, hipGetLastError());
+    return CIRCKIT_OK;
+}
+
+int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records, const circkit_window* windows,
+                           uint64_t n_windows, uint8_t* out_bytes, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    if (!out_offsets || (n_records && !offsets) || (n_windows && !windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n_records; ++i)
+        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    const uint64_t nb = n_records ? offsets[n_records] : 0;
+    if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    WindowsState* S = state(c);
+    int rc;
+    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
+    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
+    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
+    // the offsets first: the staging for the bytes is sized by the total they end in (it cannot overlap the staged payload)
+    if ((rc = launch_offsets(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
+    if ((rc = copy_totals(c, S))) return rc;
+    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
+    const uint64_t B = S->h_totals[T_TOTAL];
+    if (total) *total = B;
+    if (S->h_totals[T_REFUSED]) return check_totals(c, S->h_totals, out_capacity);
+    if (B) {
+        if (!out_bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+        if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = launch_gather(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, S->d_out_off, S->d_out))) return rc;
+        CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
+        CK_HIP(c, hipStreamSynchronize(st));
+    }
+    return check_totals(c, S->h_totals, out_capacity);
+}
+
+}  // extern "C"

@@ -385,6 +385,66 @@ int circkit_monomers_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_
                            const uint64_t* full_len, uint8_t* out_bytes, uint64_t* out_offsets, uint64_t* out_src,
                            uint32_t* kept_end, uint64_t* n_kept);
 
+/* ---- cyclic windows (`circkit rotate` / `cat` / `decat`, reverse complements, ORF sequences) ------ */
+/* One window: `length` bytes read cyclically from position `start` of record `record`, on the record or on its reverse
+ * complement.  With n the record's length and S the record (strand 0) or revcomp(record) (strand 1:
+ * S[j] = comp(s[n-1-j]), comp = bio 1.3.1's alphabets::dna complement, the table the canonicalize kernels use), the
+ * window's bytes are S[(start + t) mod n] for t < length: Orf::seq_with_opts (lib/src/orfs.rs:19-35) for an ORF on either
+ * strand, `&full_seq[idx..]` + `&full_seq[..idx]` of src/rotate.rs:42-43 with start = idx, the doubled record of
+ * src/concatenate.rs:21-22 with length 2n. */
+typedef struct circkit_window {
+    uint64_t length;                         /* bytes to write; may exceed the record's length: the read goes round the record */
+    uint32_t record;                         /* index into the batch */
+    uint32_t start;                          /* first symbol ON THE STRAND NAMED; any value, taken mod the record's length */
+    uint32_t strand;                         /* 0: the record; 1: revcomp(record) */
+    uint32_t reserved;                       /* 0 */
+} circkit_window;
+
+/* Packs the windows' bytes back to back: out_bytes[out_offsets[k] .. out_offsets[k+1]) = window k.  Device pointers; the call
+ * only enqueues work on the ctx stream.
+ *   d_windows      n_windows windows (8-byte aligned); never written
+ *   d_out_bytes    room for out_capacity bytes; must not overlap the input payload
+ *   d_out_offsets  uint64[n_windows + 1], always written in full, d_out_offsets[0] = 0
+ * A window on a record of 0 symbols writes no bytes whatever its length (the reference's cycle() over an empty slice yields
+ * nothing).  A window with record >= n_records, strand > 1, reserved != 0, or on a record of 2^32 symbols or more is INVALID:
+ * it is counted, written as an empty window and never dereferenced.  Lengths add up saturating: a total that does not fit 64
+ * bits is UINT64_MAX, which no capacity holds.  When the total exceeds out_capacity, or [d_out_bytes, d_out_bytes + total)
+ * overlaps the input payload (the offsets are the device's, so the device checks), no byte of d_out_bytes is written;
+ * d_out_offsets is written all the same.  Null d_windows / d_out_offsets (or d_bytes / d_offsets with records, or d_out_bytes
+ * with a capacity) and n_windows > 0: INVALID_ARG.  offsets[0] need not be 0; no pointer but d_windows needs any alignment. */
+int circkit_windows_gather_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                  const circkit_window* d_windows, uint64_t n_windows, uint8_t* d_out_bytes,
+                                  uint64_t out_capacity, uint64_t* d_out_offsets);
+/* Waits for the most recent windows gather of this ctx (device or host form): *total_bytes = out_offsets[n_windows],
+ * *n_invalid = its invalid windows.  CIRCKIT_ERR_OOM when the total exceeded the capacity, CIRCKIT_ERR_INVALID_ARG when the
+ * output overlapped the payload or n_invalid != 0 (with n_invalid != 0 and nothing else wrong the valid windows ARE written). */
+int circkit_windows_status(circkit_ctx* ctx, uint64_t* total_bytes, uint64_t* n_invalid);
+
+/* One window per record, written on the device from the offsets (no host round trip); restates src/rotate.rs:20-43 and
+ * src/concatenate.rs:21-22,45 for a record of n symbols:
+ *   ROTATE_BASES    s = bases;  ROTATE_PERCENT  s = floor(n as f64 * percent) as i64 (Rust's `as`: saturating, NaN = 0)
+ *                   idx = n - (s mod n) for s >= 0, |s| mod n otherwise (|i64::MIN| = 2^63); {n, i, idx mod n, 0}
+ *                   bases == 0 / percent == 0.0 (-0.0 too): INVALID_ARG, "Rotation by 0 is not allowed", nothing enqueued
+ *   CAT             {2n, i, 0, 0}      DECAT  {n / 2, i, 0, 0}      REVCOMP  {n, i, 0, 1}
+ * A record of 0 symbols gets an empty window for every kind (the reference's `% 0` panics); a record of 2^32 symbols or more
+ * a window the gather counts as invalid.  An unknown kind, or n_records > 2^32 - 1: INVALID_ARG. */
+enum { CIRCKIT_WINDOWS_ROTATE_BASES, CIRCKIT_WINDOWS_ROTATE_PERCENT, CIRCKIT_WINDOWS_CAT, CIRCKIT_WINDOWS_DECAT, CIRCKIT_WINDOWS_REVCOMP };
+int circkit_windows_of_records_device(circkit_ctx* ctx, const uint64_t* d_offsets, uint64_t n_records, uint32_t kind,
+                                      int64_t bases, double percent, circkit_window* d_windows);
+/* One window per ORF of a circkit_orfs_batch_device result: record = the record whose range of d_orf_offsets holds the ORF
+ * (none: an invalid window), start / strand as the ORF's, length = orf.length - (include_stop ? 0 : 3), 0 below that
+ * (`--include-stop`, src/orfs.rs:110-152).  The gather of these windows over the ORF batch's records is what `circkit orfs`
+ * writes as sequence lines, in the list's order. */
+int circkit_orfs_windows_device(circkit_ctx* ctx, const uint64_t* d_orf_offsets, const circkit_orf* d_orfs, uint64_t n_records,
+                                uint64_t n_orfs, int include_stop, circkit_window* d_windows);
+/* circkit_windows_gather_device with HOST buffers; synchronizes.  out_offsets (n_windows + 1) and *total are always written;
+ * when *total > out_capacity nothing is written to out_bytes and the call returns CIRCKIT_ERR_OOM, so that the caller can
+ * grow its buffer and call again.  Invalid windows: CIRCKIT_ERR_INVALID_ARG after the valid ones were written.  offsets[0]
+ * must be 0 and the offsets must not decrease. */
+int circkit_windows_gather(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                           const circkit_window* windows, uint64_t n_windows, uint8_t* out_bytes, uint64_t out_capacity,
+                           uint64_t* out_offsets, uint64_t* total);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
