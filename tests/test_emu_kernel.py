@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests import seqsets
+from tests import length_sets, seqsets
 from tests.emu import emu
 
 
@@ -522,24 +522,7 @@ def test_register_routine_with_n_mask(staged):
     variant (N packed as G, the reverse strand shows C, a mask word beside the strand word) -- every length class of the
     periodic extension, both strands, N next to the minimal window; planted A-runs with an N / G / T / C behind them put
     the N among the deciding symbols (the routine must refuse and the 4-bit routine answer)."""
-    rng = np.random.default_rng(1700 + staged)
-    comp = bytes.maketrans(b"ACGTN", b"TGCAN")
-    seqs = []
-    for L in list(range(48, 81)) + list(range(990, 1009)) + [127, 128, 129, 255, 256, 257, 511, 512, 513]:
-        s = bytearray(seqsets.random_mixed(1701 + L, 1, L, L)[0])
-        for p in rng.integers(0, L, size=max(1, L // 100)):
-            s[int(p)] = ord("N")
-        seqs.append(bytes(s))
-    for case in range(150):
-        L = int(rng.integers(200, 1009))
-        bg = bytearray(rng.choice(list(b"CGT"), size=L, p=[0.2, 0.4, 0.4]).astype(np.uint8).tobytes())
-        run = int(rng.integers(2, 15))
-        for sp in sorted(rng.choice(np.arange(10, L - 30, 25), size=int(rng.integers(1, 4)), replace=False)):
-            motif = b"A" * run + bytes(rng.choice(list(b"NGTCN"), size=1).astype(np.uint8)) + bytes(rng.choice(list(b"ACGTN"), size=5, p=[.23, .23, .23, .23, .08]).astype(np.uint8))
-            if rng.random() < 0.5:
-                motif = motif.translate(comp)[::-1]
-            bg[sp:sp + len(motif)] = motif
-        seqs.append(bytes(bg))
+    seqs = length_sets.register_routine_with_n_mask(staged)
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s) for s in seqs]
     out, idx, strand, h, status, ndef = emu.canonicalize_batch(data, offs, want_hash=False, want_aux=False, staged=staged, slice_dw=4096, n_waves=12,
@@ -552,33 +535,7 @@ def test_register_routine_with_n_mask(staged):
 
 
 # ---- canon_mixed_kernel's lean routines (canon_mixed.h): mode-3 batches that want bytes only --------------------------
-def _sprinkle(rng, s, frac, ch=ord("N")):
-    b = bytearray(s)
-    for i in range(len(b)):
-        if rng.random() < frac:
-            b[i] = ch
-    return bytes(b)
-
-
-def _mixed_batch(seed, with_n):
-    import random
-    rng = random.Random(seed)
-    seqs = seqsets.random_mixed(seed + 1, 40, 48, 1008) + seqsets.random_mixed(seed + 2, 30, 1009, 9000) + \
-        seqsets.random_mixed(seed + 3, 6, 1, 47) + [b"", b"ACGT" * 400, b"A" * 3000]
-    for n in (1100, 2500, 4097):                                          # long reverse-complement palindromes, rotations, repeats
-        h = seqsets.rand_seq(rng, n // 2)
-        seqs.append(h + seqsets.revcomp_acgt(h))
-        base = seqsets.rand_seq(rng, n)
-        k = rng.randrange(n)
-        seqs += [base, base[k:] + base[:k], seqsets.revcomp_acgt(base)]
-        u = seqsets.rand_seq(rng, 37)
-        seqs.append(seqsets.rand_seq(rng, 600) + u * 40 + seqsets.rand_seq(rng, 500))
-        seqs.append(seqsets.rand_seq(rng, 700) + b"A" * 40 + seqsets.rand_seq(rng, 900) + b"A" * 40)        # the minimal key twice
-    if with_n:
-        seqs = [_sprinkle(rng, s, 0.01) if i % 5 else s for i, s in enumerate(seqs)]
-        seqs += [_sprinkle(rng, seqsets.rand_seq(rng, 3000), 0.02, ord("-")), _sprinkle(rng, seqsets.rand_seq(rng, 500), 0.3)]
-    rng.shuffle(seqs)
-    return seqs
+_sprinkle, _mixed_batch = length_sets.sprinkle, length_sets.mixed_batch
 
 
 @pytest.mark.parametrize("with_n", [False, True])
@@ -604,21 +561,7 @@ def test_mixed_kernel_prefix_rule_and_extension_edges():
     """An N planted inside or right behind the minimal window of long records (the prefix rule's count over both strands),
     minimal windows that straddle the record's end / start (the periodic extension on both sides), at all sixteen
     alignments of the record in its first chunk."""
-    import random
-    rng = random.Random(77)
-    seqs = []
-    for k in range(48):
-        n = rng.randint(1100, 2600)
-        s = bytearray(seqsets.rand_seq(rng, n, b"CGT"))
-        pos = rng.choice([0, 1, 7, n - 1, n - 9, n - 16, n - 17, n // 2])
-        for i in range(18):
-            s[(pos + i) % n] = ord("A")                                   # the minimal key, wrapping around the end for some
-        if k % 3 == 0:
-            s[(pos + rng.randint(3, 22)) % n] = ord("N")                 # ...with an N inside or just behind it
-        if k % 3 == 1:
-            s = bytearray(seqsets.revcomp_acgt(bytes(s).replace(b"N", b"A")))   # the reverse strand wins
-            s[rng.randrange(n)] = ord("N")
-        seqs.append(bytes(s) + seqsets.rand_seq(rng, k % 16, b"G"))       # shifts the next record's alignment
+    seqs = length_sets.mixed_prefix_rule_and_extension_edges()
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     for alpha in (True, False):
@@ -635,20 +578,7 @@ def test_mixed_kernel_settles_a_tied_minimal_key():
     -- one such record in a million-record batch used to be a one-wave pass of stage A behind everything else.  Planted:
     the same minimal 16-mer two to five times, followed by different symbols (a run of 17 or 18 A as well: two or three
     owners side by side); periodic records still move on."""
-    import random
-    rng = random.Random(91)
-    seqs = []
-    for k in range(40):
-        n_runs = rng.randint(2, 5)
-        run = b"A" * (16 if k % 5 else rng.randint(17, 18))
-        parts = []
-        for _ in range(n_runs):
-            parts.append(run + seqsets.rand_seq(rng, rng.randint(200, 900), b"CGT"))
-        s = b"".join(parts)
-        if k % 4 == 0:
-            s = seqsets.revcomp_acgt(s)                                   # the reverse strand wins
-        seqs.append(s + seqsets.rand_seq(rng, k % 16, b"G"))
-    seqs += [seqsets.rand_seq(rng, 700, b"CGT") * 3, b"ACGT" * 500]       # periods: stage A's
+    seqs = length_sets.mixed_tied_minimal_key()
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     out, _, _, _, status, ndef = emu.canonicalize_batch(data, offs, want_hash=False, want_aux=False, staged=0, slice_dw=1280, n_waves=8,
@@ -668,17 +598,7 @@ def test_mixed_kernel_winner_seen_twice_by_one_lane(with_n):
     its periodic twin, in the last words -- which then belong to the SAME lane as word 0 or 1 (64 words per row).  The
     lean routine keeps the lane's second owner word; found on the GPU as ~100 records per million of config 4 that went to
     stage A for nothing (lengths 1021..1034, 2047, 4104, 5131 ...)."""
-    import random
-    rng = random.Random(123)
-    seqs = []
-    for n in list(range(1010, 1075, 3)) + list(range(2040, 2100, 5)) + [3073, 3080, 4104, 5131]:
-        s = bytearray(seqsets.rand_seq(rng, n, b"CGT"))
-        pos = rng.choice([0, 1, 2, 9, 15, 16, 17, n - 1, n - 2, n - 15, n - 16, n - 17, n - 31])
-        for i in range(16):
-            s[(pos + i) % n] = ord("A")
-        if with_n:
-            s[(pos + 40) % n] = ord("N")
-        seqs.append((seqsets.revcomp_acgt(bytes(s).replace(b"N", b"C")) if n % 2 else bytes(s)) + seqsets.rand_seq(rng, n % 16, b"G"))
+    seqs = length_sets.mixed_winner_seen_twice_by_one_lane(with_n)
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     out, _, _, _, status, ndef = emu.canonicalize_batch(data, offs, want_hash=False, want_aux=False, staged=0, slice_dw=1368, n_waves=8,
@@ -695,18 +615,7 @@ def test_mixed_kernel_minimal_key_inside_a_reverse_complement_palindrome():
     """A minimal 16-mer inside a reverse-complement palindrome of 18 or more (AAAAAATAGCTATTTTTT) is owned by BOTH strands:
     equal minimal keys, the two rotations are compared in full by the lean routine itself (seen on the GPU: ~6 records per
     million of config 4).  Whole-record palindromes included (equal rotations: the reverse strand's bytes, identical)."""
-    import random
-    rng = random.Random(321)
-    seqs = []
-    for k in range(30):
-        half = b"A" * rng.randint(6, 9) + seqsets.rand_seq(rng, rng.randint(1, 4), b"ACGT")
-        pal = half + seqsets.revcomp_acgt(half)                          # self reverse-complementary, starts with the A run
-        body = seqsets.rand_seq(rng, rng.randint(1100, 4000), b"CGT")
-        s = body[:len(body) // 3] + pal + body[len(body) // 3:]
-        seqs.append(s + seqsets.rand_seq(rng, k % 16, b"G"))
-    for n in (1200, 2600):
-        h = seqsets.rand_seq(rng, n // 2)
-        seqs.append(h + seqsets.revcomp_acgt(h))
+    seqs = length_sets.mixed_minimal_key_inside_a_palindrome()
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     out, _, _, _, status, ndef = emu.canonicalize_batch(data, offs, want_hash=False, want_aux=False, staged=0, slice_dw=1280, n_waves=8,
@@ -724,11 +633,7 @@ def test_hash_only_batches_hash_a_view_of_the_input(staged, alpha):
     hash is not fused into the register routine (<= 240 symbols, N / gap records, everything the LDS tiers take) leave strand +
     rotation, and the xxh3 pass hashes that VIEW of the input -- no canonical bytes are written, no scratch is needed (the
     round-2 path sized one from the device's last offset, with a host synchronisation)."""
-    seqs = seqsets.random_mixed(7001, 40, 48, 1008) + seqsets.random_mixed(7002, 30, 1, 260) + seqsets.random_mixed(7003, 12, 1009, 2500) + \
-        seqsets.random_mixed(7004, 20, 30, 900, b"ACGTN") + seqsets.random_mixed(7005, 8, 10, 400, b"-ACGNT") + \
-        seqsets.random_mixed(7006, 6, 1, 300, bytes(range(0x21, 0x7F))) + seqsets.adversarial()[:60] + [b"", b"ACGTRYKMacgtn" * 30]
-    rng = np.random.default_rng(7007)
-    seqs = [seqs[i] for i in rng.permutation(len(seqs))]
+    seqs = length_sets.hash_only_view_set()
     data, offs = seqsets.pack(seqs)
     out, _, _, h, status, ndef = emu.canonicalize_batch(data, offs, want_hash=True, want_aux=False, staged=staged, slice_dw=4096, n_waves=8,
                                                         alpha=alpha, hash_only=True)
@@ -743,21 +648,7 @@ def test_mixed_kernel_n_inside_the_minimal_window_is_resolved_among_the_sharers(
     true minimum is one of the sharers, found by lean_resolve_n (exact ranks A C G N T over 32 symbols) instead of a trip
     through stage A's 4-bit mode.  Planted A-runs with an N at every offset, a second shorter A-run as the sharer, both
     strands, plus N-rich random and two-letter records."""
-    import random
-    rng = random.Random(2025)
-    seqs = [_sprinkle(rng, seqsets.rand_seq(rng, rng.randint(1009, 2600)), rng.choice([0.01, 0.03, 0.08])) for _ in range(40)]
-    seqs += [_sprinkle(rng, seqsets.rand_seq(rng, rng.randint(1009, 2200), b"AC"), 0.02) for _ in range(6)]
-    for k in range(40):
-        n = rng.randint(1100, 2400)
-        s = bytearray(seqsets.rand_seq(rng, n, b"CGT"))
-        pos, pos2 = rng.randrange(n), rng.randrange(n)
-        for i in range(rng.randint(8, 16)):
-            s[(pos + i) % n] = ord("A")
-        s[(pos + k % 13) % n] = ord("N")
-        for i in range(rng.randint(5, 10)):
-            s[(pos2 + i) % n] = ord("A")
-        s = bytes(s)
-        seqs.append(s if k % 2 else seqsets.revcomp_acgt(s.replace(b"N", b"X")).replace(b"X", b"N"))
+    seqs = length_sets.mixed_n_inside_the_minimal_window()
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     out, _, _, _, status, ndef = emu.canonicalize_batch(data, offs, want_hash=False, want_aux=False, staged=0, slice_dw=1368, n_waves=8,
@@ -776,13 +667,7 @@ def test_mixed_kernel_with_fused_xxh3(with_n, hash_only):
     records of more than 240 symbols, with N too (round 4); short N records, the short-input classes and everything stage A
     takes are hashed by the xxh3 pass -- from the bytes, or (hash_only: no bytes asked for) from their views.  Lengths around every block and
     stripe boundary."""
-    import random
-    rng = random.Random(515)
-    seqs = _mixed_batch(5150, with_n)
-    for n in (241, 255, 256, 257, 1009, 1023, 1024, 1025, 1087, 1088, 1089, 2047, 2048, 2049, 2111, 2112, 2113, 3072, 3073, 4095, 4096, 4097, 5121):
-        seqs.append(seqsets.rand_seq(rng, n))
-        seqs.append(seqsets.revcomp_acgt(seqsets.rand_seq(rng, n, b"CGT") + b"A" * 17))
-    rng.shuffle(seqs)
+    seqs = length_sets.mixed_with_fused_xxh3(with_n)
     data, offs = seqsets.pack(seqs)
     want = [seqsets.expected(O, s)[0] for s in seqs]
     out, _, _, h, status, ndef = emu.canonicalize_batch(data, offs, want_hash=True, want_aux=False, staged=0, slice_dw=1596 if with_n else 1280, n_waves=12,
@@ -843,22 +728,7 @@ def test_pair_build_two_records_per_wave(staged, hash_only):
     and off the 16-symbol grid in either half (the periodic extension's r == 0 / r != 0 forms), the limits 48 and 1008, XXH3's
     short-input classes (<= 240: left to the xxh3 pass, through a view when no bytes are written), every alignment of the
     record in its first chunk."""
-    import random
-    rng = random.Random(4100 + staged)
-    R = lambda n, al=b"ACGT": seqsets.rand_seq(rng, n, al)
-    pal = R(40)
-    pal = pal + bytes(O.revcomp(pal))                                                 # its own reverse complement
-    odd = [b"", R(7), R(47), R(1009), R(1500), R(3000), R(500)[:250] + b"N" + R(249), R(300) + b"-" + R(300), b"ACGT" * 200, b"A" * 777,
-           (R(31) * 40)[:900], pal * 8, b"T" * 48, R(100, b"AC"), bytes(range(0x30, 0x7B)) * 5]
-    good = [R(n) for n in (48, 49, 63, 64, 65, 240, 241, 255, 256, 257, 511, 512, 513, 527, 528, 529, 992, 1000, 1007, 1008)]
-    seqs = []
-    for g in good:
-        o = rng.choice(odd)
-        seqs += [g, o] if rng.random() < 0.5 else [o, g]
-    for _ in range(60):
-        seqs += [R(rng.randint(48, 1008)), R(rng.randint(48, 1008))]
-    seqs += [R(1000) for _ in range(40)]                                               # (equal lengths: the lane constants are reused)
-    seqs += [R(rng.choice([48, 64, 1008])) for _ in range(16)]
+    seqs = length_sets.pair_two_records_per_wave(staged)
     data, offs = seqsets.pack(seqs)
     for base_shift in (0, 5):
         out, _, _, h, status, ndef = emu.canonicalize_batch(data, offs, want_hash=True, want_aux=False, staged=staged, slice_dw=4096, n_waves=8,
@@ -879,15 +749,7 @@ def test_pair_build_two_records_per_wave(staged, hash_only):
 def test_pair_build_every_length():
     """canon_pair.h's lane constants (periodic extension, reverse-strand windows, output cells, XXH3 stripes) are functions of the
     two record lengths: every length 48..1008 once in either half, next to a partner of another length, bytes and hashes."""
-    import random
-    rng = random.Random(5150)
-    lens = list(range(48, 1009))
-    rng.shuffle(lens)
-    seqs = []
-    for i, n in enumerate(lens):
-        a, b = seqsets.rand_seq(rng, n), seqsets.rand_seq(rng, rng.randint(48, 1008))
-        seqs += [a, b] if i % 2 else [b, a]
-    seqs += [seqsets.rand_seq(rng, 500)] * 0 + [seqsets.rand_seq(rng, 700) for _ in range(16)]     # (the last group is never staged)
+    seqs = length_sets.pair_every_length()
     data, offs = seqsets.pack(seqs)
     out, _, _, h, status, ndef = emu.canonicalize_batch(data, offs, want_hash=True, want_aux=False, staged=15, slice_dw=4096, n_waves=8)
     assert status == 0 and ndef == 0
