@@ -88,6 +88,9 @@ SIGNATURES = {
     "circkit_windows_of_records_device": (_i, [_vp, _vp, _u64, _u32, ctypes.c_int64, ctypes.c_double, _vp]),
     "circkit_orfs_windows_device": (_i, [_vp, _vp, _vp, _u64, _u64, _i, _vp]),
     "circkit_windows_gather": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
+    "circkit_windows_translate_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "circkit_translate_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "circkit_windows_translate": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -97,6 +100,32 @@ ORF_DTYPE = np.dtype([("length", "<u8"), ("start", "<u4"), ("stop", "<u4"), ("wr
 # circkit_window (include/circkit.h)
 WINDOW_DTYPE = np.dtype([("length", "<u8"), ("record", "<u4"), ("start", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
 WINDOW_KINDS = {"rotate_bases": 0, "rotate_percent": 1, "cat": 2, "decat": 3, "revcomp": 4}
+
+
+# NCBI genetic codes as "AAs" lines: residue of codon c0 c1 c2 at 16*c0 + 4*c1 + c2 with T, C, A, G = 0..3
+_STANDARD_CODE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
+GENETIC_CODES = {1: _STANDARD_CODE, 4: _STANDARD_CODE[:14] + "W" + _STANDARD_CODE[15:], 11: _STANDARD_CODE}
+
+
+# circkit_translate_params (include/circkit.h)
+class TranslateParams(ctypes.Structure):
+    _fields_ = [("aa", ctypes.c_uint8 * 64), ("unknown", ctypes.c_uint8), ("first_as_m", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
+def translate_params(table=1, unknown="X", first_as_m=False):
+    """circkit_translate_params from Python values.  table: a key of GENETIC_CODES or 64 characters / bytes in the order of an
+    NCBI "AAs" line; unknown: the residue of a codon with a byte outside ACGT; first_as_m: write the first residue of a window
+    whose first codon is three ACGT symbols as 'M'."""
+    aa = table if isinstance(table, (str, bytes, bytearray)) else GENETIC_CODES[int(table)]
+    aa = aa.encode("latin-1") if isinstance(aa, str) else bytes(aa)
+    unk = unknown.encode("latin-1") if isinstance(unknown, str) else bytes(unknown)
+    if len(aa) != 64 or len(unk) != 1:
+        raise ValueError("a genetic code has 64 residues and `unknown` is one")
+    p = TranslateParams()
+    for k, v in enumerate(aa):
+        p.aa[k] = v
+    p.unknown, p.first_as_m = unk[0], int(bool(first_as_m))
+    return p
 
 
 class OrfParams(ctypes.Structure):
@@ -514,6 +543,45 @@ class Context:
             self._check(rc)
             return out[:total.value], out_off
 
+    # -- proteins of cyclic windows ---------------------------------------------------------------
+    def windows_translate_device(self, d_bytes, d_offsets, n_records, d_windows, n_windows, d_out_aa, out_capacity, d_out_offsets,
+                                 params=None, **kw):
+        """Enqueues circkit_windows_translate_device: the protein of window k of d_windows (WINDOW_DTYPE, device) packed into
+        d_out_aa[d_out_offsets[k] .. d_out_offsets[k + 1]).  params: a translate_params() result, or its keywords.
+        translate_status() waits and returns the totals."""
+        p = params if params is not None else translate_params(**kw)
+        self._check(self._lib.circkit_windows_translate_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), _ptr(d_windows),
+                                                               int(n_windows), ctypes.byref(p), _ptr(d_out_aa), int(out_capacity),
+                                                               _ptr(d_out_offsets)))
+
+    def translate_status(self):
+        """Waits for the last translate; returns (total residues, invalid windows).  Raises CirckitError as windows_status does."""
+        t, bad = _u64(0), _u64(0)
+        self._check(self._lib.circkit_translate_status(self._h, ctypes.byref(t), ctypes.byref(bad)))
+        return t.value, bad.value
+
+    def windows_translate(self, data, offsets, windows, params=None, capacity=None, **kw):
+        """The windows' proteins of a host CSR batch, packed: (aa_bytes, aa_offsets).  windows: an array of WINDOW_DTYPE; params or
+        the keywords of translate_params.  Grows its buffer (capacity: its first size) to the reported total and runs again, as
+        windows_gather does; invalid windows raise CirckitError."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        windows = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+        p = params if params is not None else translate_params(**kw)
+        n, m = len(offsets) - 1, len(windows)
+        out_off = np.zeros(m + 1, dtype=np.uint64)
+        cap = max(len(data) // 3, 1) if capacity is None else max(int(capacity), 1)
+        while True:
+            out = np.empty(cap, dtype=np.uint8)
+            total = _u64(0)
+            rc = self._lib.circkit_windows_translate(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(windows) if m else None,
+                                                     m, ctypes.byref(p), _ptr(out), cap, _ptr(out_off), ctypes.byref(total))
+            if rc == -5 and cap < total.value < 2 ** 64 - 1:      # grow to the reported total and run again
+                cap = total.value
+                continue
+            self._check(rc)
+            return out[:total.value], out_off
+
     def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
         """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
         import torch
@@ -600,6 +668,52 @@ class Context:
                 self.windows_status()
             orfs = d_orfs.cpu().numpy().view(ORF_DTYPE)[:n_orfs].copy()
             return (d_orf_off.cpu().numpy().view(np.uint64), orfs, d_seq[:total.value].cpu().numpy(), d_seq_off.cpu().numpy().view(np.uint64))
+
+    def orf_proteins(self, data, offsets, include_stop=False, table=1, unknown="X", first_as_m=False, **orf_kw):
+        """The ORFs of a host CSR batch of normalized records and their proteins: (orf_offsets, orfs, aa_bytes, aa_offsets), shaped
+        like orf_sequences' result, ORF k's protein aa_bytes[aa_offsets[k] .. aa_offsets[k + 1]) the translation of the sequence
+        orf_sequences returns for it (with include_stop it ends in the table's stop residue).  One copy in; the ORF batch, the
+        windows and the translation on the device; then the copy home.  table / unknown / first_as_m as translate_params, the
+        other keywords as orf_params."""
+        import torch
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        p = orf_params(**orf_kw)
+        tp = translate_params(table=table, unknown=unknown, first_as_m=first_as_m)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d_bytes = torch.from_numpy(data).to(dev) if len(data) else torch.zeros(1, dtype=torch.uint8, device=dev)
+            d_offs = torch.from_numpy(offsets.view(np.int64)).to(dev)
+            torch.cuda.current_stream().synchronize()         # the copies are torch's, the kernels the ctx stream's
+            d_orf_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            cap = max(n, 1) * 4
+            while True:
+                d_orfs = torch.empty(cap * ORF_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                self.orfs_batch_device(d_bytes, d_offs, n, d_orf_off, d_orfs, cap, params=p)
+                t = _u64(0)
+                rc = self._lib.circkit_orfs_status(self._h, ctypes.byref(t))
+                if rc == -5 and t.value > cap:                    # grow to the reported total and run again
+                    cap = t.value
+                    continue
+                self._check(rc)
+                break
+            n_orfs = t.value
+            d_win = torch.empty(max(n_orfs, 1) * WINDOW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            d_aa_off = torch.empty(n_orfs + 1, dtype=torch.int64, device=dev)
+            self.orfs_windows_device(d_orf_off, d_orfs, n, n_orfs, d_win, include_stop=include_stop)
+            # the offsets first (a translate without room reports the total), then the translate into a buffer of that size
+            self.windows_translate_device(d_bytes, d_offs, n, d_win, n_orfs, None, 0, d_aa_off, params=tp)
+            total = _u64(0)
+            rc = self._lib.circkit_translate_status(self._h, ctypes.byref(total), None)
+            if rc != -5:
+                self._check(rc)
+            d_aa = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+            if total.value:
+                self.windows_translate_device(d_bytes, d_offs, n, d_win, n_orfs, d_aa, total.value, d_aa_off, params=tp)
+                self.translate_status()
+            orfs = d_orfs.cpu().numpy().view(ORF_DTYPE)[:n_orfs].copy()
+            return (d_orf_off.cpu().numpy().view(np.uint64), orfs, d_aa[:total.value].cpu().numpy(), d_aa_off.cpu().numpy().view(np.uint64))
 
     # -- monomerize -----------------------------------------------------------------------------
     def monomerize_batch_device(self, d_bytes, d_offsets, n_records, d_end, params=None, **kw):
@@ -781,6 +895,14 @@ def revcomp_batch(data, offsets):
 
 def orf_sequences(data, offsets, include_stop=False, **orf_params):
     return default_context().orf_sequences(data, offsets, include_stop=include_stop, **orf_params)
+
+
+def windows_translate(data, offsets, windows, **kw):
+    return default_context().windows_translate(data, offsets, windows, **kw)
+
+
+def orf_proteins(data, offsets, include_stop=False, **kw):
+    return default_context().orf_proteins(data, offsets, include_stop=include_stop, **kw)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

@@ -10,6 +10,10 @@
 //   windows_gather_kernel      window_gather.h gather_tile over the output tiles, unless the scan refused the gather
 // The sums saturate (window_gather.h sat_add), so out_offsets never decreases whatever lengths the windows name.  The totals
 // stay in device memory and are copied to pinned memory behind the gather: circkit_windows_status waits and reads them.
+// A translate (window_translate.h) is the same five steps with its own first and last: windows_residues_kernel counts residues
+// (a third of the bytes, rounded down), the three scan kernels run as they are, windows_translate_kernel runs translate_tile
+// over the output tiles.  Its totals are its own, so circkit_windows_status and circkit_translate_status each answer for the
+// most recent call of their kind whatever ran in between.
 // windows_of_records_kernel and orfs_windows_kernel write the window lists of rotate / cat / decat / revcomp and of an ORF
 // batch from what the device already holds.
 #include <hip/hip_runtime.h>
@@ -19,10 +23,12 @@
 #include "../../include/circkit.h"
 #include "ck_ctx.h"
 #include "window_gather.h"
+#include "window_translate.h"
 
 using ck_windows::Window;
 
 static_assert(sizeof(Window) == sizeof(circkit_window) && sizeof(Window) == 24, "device window layout");
+static_assert(sizeof(circkit_translate_params) == 72, "translate params layout");
 static_assert((int)ck_windows::KIND_ROTATE_BASES == CIRCKIT_WINDOWS_ROTATE_BASES && (int)ck_windows::KIND_ROTATE_PERCENT == CIRCKIT_WINDOWS_ROTATE_PERCENT &&
               (int)ck_windows::KIND_CAT == CIRCKIT_WINDOWS_CAT && (int)ck_windows::KIND_DECAT == CIRCKIT_WINDOWS_DECAT &&
               (int)ck_windows::KIND_REVCOMP == CIRCKIT_WINDOWS_REVCOMP, "window kinds");
@@ -44,6 +50,18 @@ __global__ __launch_bounds__(WIN_WG) void windows_lengths_kernel(const uint64_t*
     for (uint64_t k = (uint64_t)blockIdx.x * WIN_WG + threadIdx.x; k < m; k += stride) {
         bool invalid;
         out_offsets[k + 1] = ck_windows::effective_length(windows[k], offsets, n_records, &invalid);
+        if (invalid) atomicAdd((unsigned long long*)&totals[T_INVALID], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(WIN_WG) void windows_residues_kernel(const uint64_t* __restrict__ offsets, uint64_t n_records,
+                                                                  const Window* __restrict__ windows, uint64_t m,
+                                                                  uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ totals)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * WIN_WG;
+    for (uint64_t k = (uint64_t)blockIdx.x * WIN_WG + threadIdx.x; k < m; k += stride) {
+        bool invalid;
+        out_offsets[k + 1] = ck_translate::residue_length(windows[k], offsets, n_records, &invalid);
         if (invalid) atomicAdd((unsigned long long*)&totals[T_INVALID], 1ull);
     }
 }
@@ -143,6 +161,31 @@ __global__ __launch_bounds__(64 * ck_windows::GATHER_WAVES) void windows_gather_
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_windows::gather_tile(G, t);
 }
 
+__global__ __launch_bounds__(64 * ck_translate::TRANSLATE_WAVES) void windows_translate_kernel(
+    const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n_records, const Window* __restrict__ windows, uint64_t m,
+    const uint64_t* __restrict__ out_offsets, const uint64_t* __restrict__ totals, const uint8_t* __restrict__ comp, circkit_translate_params params,
+    uint8_t* __restrict__ out)
+{
+    __shared__ uint8_t cls_lds[2][ck_translate::CLASS_ENTRIES];
+    __shared__ uint8_t residue_lds[128];
+    ck_translate::fill_tables(threadIdx.x, 64 * ck_translate::TRANSLATE_WAVES, comp, params.aa, params.unknown, cls_lds[0], cls_lds[1], residue_lds);
+    __syncthreads();
+    if (totals[T_REFUSED]) return;                    // the same for the whole grid
+    ck_translate::Translate T;
+    T.bytes = bytes; T.offsets = offsets;
+    T.p0 = offsets[0]; T.p1 = offsets[n_records];
+    T.windows = windows; T.out_offsets = out_offsets;
+    T.m = m; T.B = totals[T_TOTAL];
+    T.cls0 = cls_lds[0]; T.cls1 = cls_lds[1];
+    T.residue = residue_lds;
+    T.first_as_m = params.first_as_m;
+    T.out = out;
+    if (T.B == 0) return;
+    const uint64_t n_gran = (((uint64_t)(uintptr_t)out & 15u) + T.B + 15) / 16;
+    const uint64_t n_tiles = (n_gran + ck_translate::TILE_GRANULES - 1) / ck_translate::TILE_GRANULES;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_translate::translate_tile(T, t);
+}
+
 __global__ __launch_bounds__(WIN_WG) void windows_of_records_kernel(const uint64_t* __restrict__ offsets, uint64_t n, uint32_t kind, int64_t bases,
                                                                     double percent, Window* __restrict__ windows)
 {
@@ -175,13 +218,18 @@ __global__ __launch_bounds__(WIN_WG) void orfs_windows_kernel(const uint64_t* __
     }
 }
 
-struct WindowsState {
-    uint64_t* d_totals = nullptr;    // [T_WORDS] of the most recent gather, device
-    uint64_t* h_totals = nullptr;    // the same, page-locked host memory: valid once the ctx stream has run past the copy
-    uint64_t capacity = 0;           // of the most recent gather, for the status message
+// the totals of the most recent gather, or of the most recent translate: each kind of call has its own
+struct Totals {
+    uint64_t* d = nullptr;           // [T_WORDS], device
+    uint64_t* h = nullptr;           // the same, page-locked host memory: valid once the ctx stream has run past the copy
+    uint64_t capacity = 0;           // of that call, for the status message
     bool any = false;
+};
+
+struct WindowsState {
+    Totals gather, translate;
     uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
-    // circkit_windows_gather's staging (grow only)
+    // the staging of circkit_windows_gather and circkit_windows_translate (grow only)
     uint8_t* d_in = nullptr; uint64_t cap_in = 0;
     uint64_t* d_off = nullptr; uint64_t cap_off = 0;
     Window* d_win = nullptr; uint64_t cap_win = 0;
@@ -193,9 +241,10 @@ void release_state(void* p)
 {
     WindowsState* S = (WindowsState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_totals, S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
+    void* ptrs[] = { S->gather.d, S->translate.d, S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    if (S->gather.h) (void)hipHostFree(S->gather.h);
+    if (S->translate.h) (void)hipHostFree(S->translate.h);
     delete S;
 }
 
@@ -222,28 +271,31 @@ uint32_t lane_grid(uint64_t items)
     return (uint32_t)(grid > WIN_MAX_GRID ? WIN_MAX_GRID : grid);
 }
 
-// lengths, the scan with its refusals, and the copy of the totals: out_offsets is complete and S->h_totals valid once the stream
-// has run past it.  d_out is only compared with the payload.
-int launch_offsets(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+// lengths (in bytes, or in residues for a translate), the scan with its refusals, and the copy of the totals: out_offsets is
+// complete and R->h valid once the stream has run past it.  d_out is only compared with the payload.
+int launch_offsets(circkit_ctx* c, WindowsState* S, Totals* R, bool residues, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
                    const Window* d_windows, uint64_t m, const uint8_t* d_out, uint64_t capacity, uint64_t* d_out_offsets)
 {
-    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
-    if (!S->h_totals) CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    if (!R->d) CK_HIP(c, hipMalloc((void**)&R->d, T_WORDS * sizeof(uint64_t)));
+    if (!R->h) CK_HIP(c, hipHostMalloc((void**)&R->h, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
     const uint64_t tiles = (m + WSCAN_TILE - 1) / WSCAN_TILE;
     int rc;
     if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    CK_HIP(c, hipMemsetAsync(R->d, 0, T_WORDS * sizeof(uint64_t), st));
     if (m) {
-        hipLaunchKernelGGL(windows_lengths_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, S->d_totals);
+        if (residues)
+            hipLaunchKernelGGL(windows_residues_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
+        else
+            hipLaunchKernelGGL(windows_lengths_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
         hipLaunchKernelGGL(windows_tile_sums_kernel, dim3((uint32_t)tiles), dim3(WSCAN_WG), 0, st, (const uint64_t*)d_out_offsets + 1, m, S->d_sums);
     }
     hipLaunchKernelGGL(windows_scan_sums_kernel, dim3(1), dim3(WSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, m ? n_records : 0, d_out, capacity,
-                       d_out_offsets, S->d_totals);
+                       d_out_offsets, R->d);
     if (m) hipLaunchKernelGGL(windows_apply_kernel, dim3((uint32_t)tiles), dim3(WSCAN_WG), 0, st, d_out_offsets + 1, m, (const uint64_t*)S->d_sums);
     CK_HIP(c, hipGetLastError());
-    S->capacity = capacity;
-    S->any = true;
+    R->capacity = capacity;
+    R->any = true;
     return CIRCKIT_OK;
 }
 
@@ -252,14 +304,24 @@ int launch_gather(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, const
 {
     if (!m || !n_records) return CIRCKIT_OK;           // no window writes a byte
     hipLaunchKernelGGL(windows_gather_kernel, dim3(GATHER_GRID), dim3(64 * ck_windows::GATHER_WAVES), 0, ck_ctx_stream(c), d_bytes, d_offsets, n_records,
-                       d_windows, m, d_out_offsets, (const uint64_t*)S->d_totals, ck_ctx_complement(c), d_out);
+                       d_windows, m, d_out_offsets, (const uint64_t*)S->gather.d, ck_ctx_complement(c), d_out);
     CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
 }
 
-int copy_totals(circkit_ctx* c, WindowsState* S)
+int launch_translate(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records, const Window* d_windows,
+                     uint64_t m, const circkit_translate_params& params, const uint64_t* d_out_offsets, uint8_t* d_out)
 {
-    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
+    if (!m || !n_records) return CIRCKIT_OK;           // no window writes a residue
+    hipLaunchKernelGGL(windows_translate_kernel, dim3(GATHER_GRID), dim3(64 * ck_translate::TRANSLATE_WAVES), 0, ck_ctx_stream(c), d_bytes, d_offsets,
+                       n_records, d_windows, m, d_out_offsets, (const uint64_t*)S->translate.d, ck_ctx_complement(c), params, d_out);
+    CK_HIP(c, hipGetLastError());
+    return CIRCKIT_OK;
+}
+
+int copy_totals(circkit_ctx* c, Totals* R)
+{
+    CK_HIP(c, hipMemcpyAsync(R->h, R->d, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
     return CIRCKIT_OK;
 }
 
@@ -271,6 +333,25 @@ int check_totals(circkit_ctx* c, const uint64_t* t, uint64_t capacity)
                        (unsigned long long)capacity);
     if (t[T_REFUSED]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_bytes overlaps the input payload: nothing was written");
     if (t[T_INVALID]) return ck_fail(c, CIRCKIT_ERR_INVALID_ARG, "%llu invalid windows were written as empty ones", (unsigned long long)t[T_INVALID]);
+    return CIRCKIT_OK;
+}
+
+int check_translate_totals(circkit_ctx* c, const uint64_t* t, uint64_t capacity)
+{
+    if (t[T_REFUSED] == REFUSED_CAPACITY)
+        return ck_fail(c, CIRCKIT_ERR_OOM, "the windows translate to %llu residues, the buffer holds %llu: nothing was written",
+                       (unsigned long long)t[T_TOTAL], (unsigned long long)capacity);
+    if (t[T_REFUSED]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_aa overlaps the input payload: nothing was written");
+    if (t[T_INVALID]) return ck_fail(c, CIRCKIT_ERR_INVALID_ARG, "%llu invalid windows were translated as empty ones", (unsigned long long)t[T_INVALID]);
+    return CIRCKIT_OK;
+}
+
+int check_translate_params(circkit_ctx* c, const circkit_translate_params* p)
+{
+    if (!p) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null translate params");
+    if (p->first_as_m > 1) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "first_as_m must be 0 or 1");
+    for (uint8_t r : p->reserved)
+        if (r) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "the reserved bytes of circkit_translate_params must be 0");
     return CIRCKIT_OK;
 }
 
@@ -289,9 +370,11 @@ int circkit_windows_gather_device(circkit_ctx* c, const uint8_t* d_bytes, const 
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     WindowsState* S = state(c);
     int rc;
-    if ((rc = launch_offsets(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_bytes, out_capacity, d_out_offsets))) return rc;
+    if ((rc = launch_offsets(c, S, &S->gather, false, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_bytes, out_capacity,
+                             d_out_offsets)))
+        return rc;
     if ((rc = launch_gather(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_offsets, d_out_bytes))) return rc;
-    return copy_totals(c, S);
+    return copy_totals(c, &S->gather);
 }
 
 int circkit_windows_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* n_invalid)
@@ -300,10 +383,10 @@ int circkit_windows_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* n_in
     WindowsState* S = state(c);
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t none[T_WORDS] = { 0, 0, 0 };
-    const uint64_t* t = S->any ? S->h_totals : none;
+    const uint64_t* t = S->gather.any ? S->gather.h : none;
     if (total_bytes) *total_bytes = t[T_TOTAL];
     if (n_invalid) *n_invalid = t[T_INVALID];
-    return check_totals(c, t, S->capacity);
+    return check_totals(c, t, S->gather.capacity);
 }
 
 int circkit_windows_of_records_device(circkit_ctx* c, const uint64_t* d_offsets, uint64_t n_records, uint32_t kind, int64_t bases, double percent,
@@ -361,13 +444,13 @@ int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
     // the offsets first: the staging for the bytes is sized by the total they end in (it cannot overlap the staged payload)
-    if ((rc = launch_offsets(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = copy_totals(c, S))) return rc;
+    if ((rc = launch_offsets(c, S, &S->gather, false, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
+    if ((rc = copy_totals(c, &S->gather))) return rc;
     CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
-    const uint64_t B = S->h_totals[T_TOTAL];
+    const uint64_t B = S->gather.h[T_TOTAL];
     if (total) *total = B;
-    if (S->h_totals[T_REFUSED]) return check_totals(c, S->h_totals, out_capacity);
+    if (S->gather.h[T_REFUSED]) return check_totals(c, S->gather.h, out_capacity);
     if (B) {
         if (!out_bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
         if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
@@ -375,7 +458,81 @@ int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
         CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
         CK_HIP(c, hipStreamSynchronize(st));
     }
-    return check_totals(c, S->h_totals, out_capacity);
+    return check_totals(c, S->gather.h, out_capacity);
+}
+
+int circkit_windows_translate_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                     const circkit_window* d_windows, uint64_t n_windows, const circkit_translate_params* params, uint8_t* d_out_aa,
+                                     uint64_t out_capacity, uint64_t* d_out_offsets)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_translate_params(c, params))) return rc;
+    if (n_windows && (!d_windows || !d_out_offsets || (out_capacity && !d_out_aa))) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows && n_records && (!d_bytes || !d_offsets)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    WindowsState* S = state(c);
+    if ((rc = launch_offsets(c, S, &S->translate, true, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_aa, out_capacity,
+                             d_out_offsets)))
+        return rc;
+    if ((rc = launch_translate(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, *params, d_out_offsets, d_out_aa))) return rc;
+    return copy_totals(c, &S->translate);
+}
+
+int circkit_translate_status(circkit_ctx* c, uint64_t* total_residues, uint64_t* n_invalid)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    WindowsState* S = state(c);
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    const uint64_t none[T_WORDS] = { 0, 0, 0 };
+    const uint64_t* t = S->translate.any ? S->translate.h : none;
+    if (total_residues) *total_residues = t[T_TOTAL];
+    if (n_invalid) *n_invalid = t[T_INVALID];
+    return check_translate_totals(c, t, S->translate.capacity);
+}
+
+int circkit_windows_translate(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records, const circkit_window* windows,
+                              uint64_t n_windows, const circkit_translate_params* params, uint8_t* out_aa, uint64_t out_capacity,
+                              uint64_t* out_offsets, uint64_t* total)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_translate_params(c, params))) return rc;
+    if (!out_offsets || (n_records && !offsets) || (n_windows && !windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n_records; ++i)
+        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    const uint64_t nb = n_records ? offsets[n_records] : 0;
+    if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    WindowsState* S = state(c);
+    Totals* R = &S->translate;
+    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
+    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
+    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
+    // the offsets first: the staging for the residues is sized by the total they end in (it cannot overlap the staged payload)
+    if ((rc = launch_offsets(c, S, R, true, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
+    if ((rc = copy_totals(c, R))) return rc;
+    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
+    const uint64_t B = R->h[T_TOTAL];
+    if (total) *total = B;
+    if (R->h[T_REFUSED]) return check_translate_totals(c, R->h, out_capacity);
+    if (B) {
+        if (!out_aa) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+        if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = launch_translate(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, *params, S->d_out_off, S->d_out))) return rc;
+        CK_HIP(c, hipMemcpyAsync(out_aa, S->d_out, B, hipMemcpyDeviceToHost, st));
+        CK_HIP(c, hipStreamSynchronize(st));
+    }
+    return check_translate_totals(c, R->h, out_capacity);
 }
 
 }  // extern "C"

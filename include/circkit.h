@@ -445,6 +445,44 @@ int circkit_windows_gather(circkit_ctx* ctx, const uint8_t* bytes, const uint64_
                            const circkit_window* windows, uint64_t n_windows, uint8_t* out_bytes, uint64_t out_capacity,
                            uint64_t* out_offsets, uint64_t* total);
 
+/* ---- proteins of cyclic windows ------------------------------------------------------------------ */
+/* With L the bytes circkit_windows_gather_device writes for a window (0 on an empty record and for an invalid window) and S,
+ * n as above, the window's protein has L / 3 residues (one or two trailing symbols are ignored); residue t is
+ *   aa[16 c(S[(start + 3t) mod n]) + 4 c(S[(start + 3t + 1) mod n]) + c(S[(start + 3t + 2) mod n])]
+ * with c('T') = 0, c('C') = 1, c('A') = 2, c('G') = 3: the order of NCBI's genetic-code strings.  A codon with any other byte
+ * (N, '-', lower case: batches are normalized) is `unknown`.  On a record of 1 or 2 symbols a codon reads a symbol more than
+ * once.  With first_as_m, residue 0 of every window whose first codon is three ACGT symbols is 'M' whatever the table says (an
+ * alternative start codon reads as methionine); an unknown first codon stays `unknown`.  The protein of window k is the plain
+ * translation of the bytes circkit_windows_gather_device writes for window k. */
+typedef struct circkit_translate_params {
+    uint8_t aa[64];                          /* residue per codon, index 16*c0 + 4*c1 + c2 with T,C,A,G = 0..3 (an NCBI "AAs" line) */
+    uint8_t unknown;                         /* residue of a codon with a byte outside ACGT, e.g. 'X' */
+    uint8_t first_as_m;                      /* 0 / 1 */
+    uint8_t reserved[6];                     /* 0 */
+} circkit_translate_params;
+
+/* Packs the windows' proteins back to back: out_aa[out_offsets[k] .. out_offsets[k+1]) = window k's residues.  The contract is
+ * circkit_windows_gather_device's with residues in place of bytes: device pointers, the call only enqueues work;
+ * d_out_offsets[0 .. n_windows] is always written in full and the sums saturate; when the total exceeds out_capacity, or
+ * [d_out_aa, d_out_aa + total) overlaps the input payload (the device decides), no byte of d_out_aa is written; invalid windows
+ * are counted and empty, their neighbours are written; the null-pointer and alignment rules are the gather's.  Null params,
+ * first_as_m > 1 or a reserved byte in use: INVALID_ARG, nothing enqueued.  With the stop codon in the window
+ * (circkit_orfs_windows_device, include_stop) the protein ends in the table's stop residue. */
+int circkit_windows_translate_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                     const circkit_window* d_windows, uint64_t n_windows, const circkit_translate_params* params,
+                                     uint8_t* d_out_aa, uint64_t out_capacity, uint64_t* d_out_offsets);
+/* Waits for the most recent translate of this ctx (device or host form): *total_residues = out_offsets[n_windows], *n_invalid =
+ * its invalid windows; the return values are circkit_windows_status's.  The totals are the translate's own: this call and
+ * circkit_windows_status each answer for the most recent call of their kind, whatever ran in between. */
+int circkit_translate_status(circkit_ctx* ctx, uint64_t* total_residues, uint64_t* n_invalid);
+/* circkit_windows_translate_device with HOST buffers; synchronizes.  out_offsets (n_windows + 1) and *total are always written;
+ * when *total > out_capacity nothing is written to out_aa and the call returns CIRCKIT_ERR_OOM, so that the caller can grow
+ * its buffer and call again.  Invalid windows: CIRCKIT_ERR_INVALID_ARG after the valid ones were written.  offsets[0] must be
+ * 0 and the offsets must not decrease. */
+int circkit_windows_translate(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                              const circkit_window* windows, uint64_t n_windows, const circkit_translate_params* params,
+                              uint8_t* out_aa, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
