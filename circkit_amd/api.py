@@ -69,6 +69,9 @@ SIGNATURES = {
     "circkit_fasta_offsets": (_vp, [_vp]),
     "circkit_fasta_record": (_i, [_vp, _u64] + [ctypes.POINTER(_sz)] * 4),
     "circkit_fasta_free": (None, [_vp]),
+    "circkit_fasta_parse_device": (_i, [_vp, _vp, _u64, _i, _i, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "circkit_fasta_parse_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 3),
+    "circkit_fasta_parse_text": (_i, [_vp, _vp, _u64, _i, _i, _vp, _u64, _vp, _u64, _vp, _vp] + [ctypes.POINTER(_u64)] * 3),
     "circkit_synth_fill_device": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "circkit_fixed_offsets_device": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "circkit_bench_copy_device": (_i, [_vp, _vp, _vp, _u64, _u32]),
@@ -99,6 +102,8 @@ ORF_NO_STOP = 0xFFFFFFFF
 ORF_DTYPE = np.dtype([("length", "<u8"), ("start", "<u4"), ("stop", "<u4"), ("wraps", "<u4"), ("strand", "<u4")])
 # circkit_window (include/circkit.h)
 WINDOW_DTYPE = np.dtype([("length", "<u8"), ("record", "<u4"), ("start", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
+# circkit_fasta_span (include/circkit.h)
+FASTA_SPAN_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])
 WINDOW_KINDS = {"rotate_bases": 0, "rotate_percent": 1, "cat": 2, "decat": 3, "revcomp": 4}
 
 
@@ -496,6 +501,69 @@ class Context:
             self._check(rc)
             return [(int(o["start"]), None if int(o["stop"]) == ORF_NO_STOP else int(o["stop"]), int(o["wraps"]), int(o["length"]))
                     for o in out[:cnt.value]]
+
+    # -- FASTA text on the device ------------------------------------------------------------------
+    def fasta_parse_device(self, d_text, n_text, d_out_bytes, byte_capacity, d_out_offsets, record_capacity, d_head=None, d_raw=None,
+                           first_chunk=True, final_chunk=True):
+        """Enqueues circkit_fasta_parse_device: the text d_text[0, n_text) (device) becomes the CSR batch d_out_bytes /
+        d_out_offsets (uint64[record_capacity + 1]); d_head / d_raw (FASTA_SPAN_DTYPE[record_capacity], device) receive the header
+        and raw sequence spans when given.  fasta_parse_status() waits and returns the counts."""
+        self._check(self._lib.circkit_fasta_parse_device(self._h, _ptr(d_text), int(n_text), int(bool(first_chunk)), int(bool(final_chunk)),
+                                                         _ptr(d_out_bytes), int(byte_capacity), _ptr(d_out_offsets), int(record_capacity),
+                                                         _ptr(d_head), _ptr(d_raw)))
+
+    def fasta_parse_status(self):
+        """Waits for the last device parse; returns (records, payload bytes, consumed).  Raises CirckitError: OOM when the
+        records or the payload exceeded the capacities (nothing was written; the message has the true counts), INVALID_ARG on the
+        format error or when the payload buffer overlapped the text."""
+        r, b, used = _u64(0), _u64(0), _u64(0)
+        self._check(self._lib.circkit_fasta_parse_status(self._h, ctypes.byref(r), ctypes.byref(b), ctypes.byref(used)))
+        return r.value, b.value, used.value
+
+    def fasta_parse_text(self, text, first_chunk=True, final_chunk=True, keep_on_device=False):
+        """fasta_parse on the device: FASTA text -> (records, normalized_bytes, offsets, consumed), records = [(head, raw_seq)].
+        One copy in, the parse on the device, one copy home (circkit_fasta_parse_text).  keep_on_device: the bytes and the offsets
+        stay on the device and are returned as torch tensors (uint8 / int64 holding the uint64 offsets); only the spans come home.
+        Raises ValueError on a format error, as fasta_parse does."""
+        text = bytes(text)
+        n = len(text)
+        cap_r = (n + 1) // 2
+        if keep_on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.device(dev):
+                d_text = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)).to(dev)
+                d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                d_off = torch.empty(cap_r + 1, dtype=torch.int64, device=dev)
+                d_spans = torch.empty((2, max(cap_r, 1), 2), dtype=torch.int64, device=dev)
+                self.fasta_parse_device(d_text, n, d_out, n, d_off, cap_r, d_spans[0], d_spans[1], first_chunk=first_chunk, final_chunk=final_chunk)
+                r, b, used = _u64(0), _u64(0), _u64(0)
+                rc = self._lib.circkit_fasta_parse_status(self._h, ctypes.byref(r), ctypes.byref(b), ctypes.byref(used))
+                if rc != OK:
+                    msg = self._lib.circkit_last_error(self._h).decode()
+                    if msg.startswith("FASTA parse error"):
+                        raise ValueError(msg)
+                    raise CirckitError(rc, msg)
+                spans = d_spans[:, :r.value].cpu().numpy().view(np.uint64)
+                data, offs = d_out[:b.value], d_off[:r.value + 1]
+                head, raw = spans[0], spans[1]
+        else:
+            buf = np.frombuffer(text, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+            data = np.empty(max(n, 1), dtype=np.uint8)
+            offs = np.zeros(cap_r + 1, dtype=np.uint64)
+            head = np.zeros((max(cap_r, 1), 2), dtype=np.uint64)
+            raw = np.zeros((max(cap_r, 1), 2), dtype=np.uint64)
+            r, b, used = _u64(0), _u64(0), _u64(0)
+            rc = self._lib.circkit_fasta_parse_text(self._h, _ptr(buf), n, int(bool(first_chunk)), int(bool(final_chunk)), _ptr(data), n, _ptr(offs),
+                                                    cap_r, _ptr(head), _ptr(raw), ctypes.byref(r), ctypes.byref(b), ctypes.byref(used))
+            if rc != OK:
+                msg = self._lib.circkit_last_error(self._h).decode()
+                if msg.startswith("FASTA parse error"):
+                    raise ValueError(msg)
+                raise CirckitError(rc, msg)
+            data, offs = data[:b.value].copy(), offs[:r.value + 1].copy()
+        recs = [(text[int(head[i][0]):int(head[i][0] + head[i][1])], text[int(raw[i][0]):int(raw[i][0] + raw[i][1])]) for i in range(r.value)]
+        return recs, data, offs, used.value
 
     # -- cyclic windows ------------------------------------------------------------------------
     def windows_gather_device(self, d_bytes, d_offsets, n_records, d_windows, n_windows, d_out_bytes, out_capacity, d_out_offsets):
@@ -903,6 +971,11 @@ def windows_translate(data, offsets, windows, **kw):
 
 def orf_proteins(data, offsets, include_stop=False, **kw):
     return default_context().orf_proteins(data, offsets, include_stop=include_stop, **kw)
+
+
+def fasta_parse_gpu(text, first_chunk=True, final_chunk=True, keep_on_device=False):
+    """fasta_parse with the parse on the GPU (Context.fasta_parse_text): the same four results."""
+    return default_context().fasta_parse_text(text, first_chunk=first_chunk, final_chunk=final_chunk, keep_on_device=keep_on_device)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

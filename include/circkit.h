@@ -501,6 +501,38 @@ int circkit_fasta_record(const circkit_fasta_batch* b, uint64_t i, size_t* head_
                          size_t* raw_len);
 void circkit_fasta_free(circkit_fasta_batch* b);
 
+/* ---- FASTA -> CSR on the device ------------------------------------------------------------------ */
+/* The device form of circkit_fasta_parse (ckhost::parse_chunk, fasta_host.cpp): the same records, spans, normalized bytes and
+ * `consumed` for the same text and flags, byte for byte -- seq_io 0.3.2's record boundaries and needletail 0.5.1
+ * normalize(_, false) (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  One difference: without first_chunk the text's first byte
+ * starts a record whatever it is, and a '\n' there is part of no header end (the host routine reads in front of the text then). */
+typedef struct circkit_fasta_span { uint64_t off, len; } circkit_fasta_span;   /* into the text */
+
+/* Parses d_text[0, n_text) into the CSR batch d_out_bytes / d_out_offsets, which circkit_canonicalize_batch_device,
+ * circkit_monomerize_batch_device, circkit_orfs_batch_device and the other batch calls take as it is.  Device pointers; the call
+ * only enqueues work on the ctx stream.  No pointer needs any alignment; the text is never written; n_text up to 2^40, 0 is valid.
+ *   d_out_offsets   uint64[record_capacity + 1]; [0] = 0 is always written
+ *   d_head, d_raw   circkit_fasta_span[record_capacity] each, or null: header and raw sequence span of every record, as
+ *                   circkit_fasta_record reports them
+ * The counts are always produced (circkit_fasta_parse_status).  When the records exceed record_capacity or the payload exceeds
+ * byte_capacity (CIRCKIT_ERR_OOM with the true counts), when [d_out_bytes, d_out_bytes + payload) overlaps the text (the device
+ * decides; CIRCKIT_ERR_INVALID_ARG) or on the format error (CIRCKIT_ERR_INVALID_ARG, the host routine's message, zero records),
+ * no payload byte, no offset beyond [0] and no span is written: grow the buffers and call again.  byte_capacity = n_text and
+ * record_capacity = (n_text + 1) / 2 always suffice.  Nothing is written outside [d_out_bytes, d_out_bytes + payload),
+ * d_out_offsets[0 .. n_records] and the first n_records spans. */
+int circkit_fasta_parse_device(circkit_ctx* ctx, const uint8_t* d_text, uint64_t n_text, int first_chunk, int final_chunk,
+                               uint8_t* d_out_bytes, uint64_t byte_capacity, uint64_t* d_out_offsets, uint64_t record_capacity,
+                               circkit_fasta_span* d_head, circkit_fasta_span* d_raw);
+/* Waits for the most recent device parse of this ctx (device or host form): its records, payload bytes and `consumed`, and its
+ * verdict as described above. */
+int circkit_fasta_parse_status(circkit_ctx* ctx, uint64_t* n_records, uint64_t* payload_bytes, uint64_t* consumed);
+/* circkit_fasta_parse_device with HOST buffers: copies the text in, parses, copies the batch home and synchronizes.  The counts
+ * are always written; on CIRCKIT_ERR_OOM nothing but they and out_offsets[0] is.  The staging is the ctx's and only grows. */
+int circkit_fasta_parse_text(circkit_ctx* ctx, const uint8_t* text, uint64_t n_text, int first_chunk, int final_chunk,
+                             uint8_t* out_bytes, uint64_t byte_capacity, uint64_t* out_offsets, uint64_t record_capacity,
+                             circkit_fasta_span* head, circkit_fasta_span* raw, uint64_t* n_records, uint64_t* payload_bytes,
+                             uint64_t* consumed);
+
 /* ---- synthetic input on the device (bench / tests) ------------------------------ */
 /* Fills d_bytes[0..n_bases) with uniform ACGT from the counter-based generator keyed by
  * (seed, first_base + i) -- the same bytes oracle/ck_oracle_synth_fill produces on the host. */
