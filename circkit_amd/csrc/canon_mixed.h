@@ -637,6 +637,15 @@ CK_DEV void canon_mixed_segment(const CanonArgs& a, uint32_t* slice, const uint3
             wave_sync();                                    // every lane is done with the slice before the next record's build
             if (r == 0) continue;
             not_acgt = NM || r == 1;
+            if (NM && r == 3) {
+                // not tried (no room in the slice, chunks outside the payload): nobody has looked at the record, and the flag makes
+                // every stage behind skip the 2-bit modes -- a pure record then needs the N-mask strand's 1.5x and a pure record with
+                // a tied minimal key the 4-bit strand, up to a refusal at the end of the line of a record that fits.  So the flag
+                // says what canon_record's own look at the first KiB says (at 1 % N that is where a long record shows it)
+                uint32_t miss = 0;
+                if (16 * lane_id() + 16 <= (uint32_t)len) (void)fast_pack(load16(a.bytes + off + 16 * lane_id()), miss);
+                not_acgt = ballot(miss != 0) != 0;
+            }
             ruled = NM && r != 3;
         }
         not_acgt = not_acgt || tried;

@@ -1320,7 +1320,12 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         return CIRCKIT_OK;
     }
     // ...sizes the global scratch for the longest record, whatever mode it turns out to need
-    if (worst_case_dw(max_len) > TIER_D_DW && (rc = ensure_gscratch(c, worst_case_dw(max_len) * 4))) return rc;
+    // (never less than the device entry points' size: on a fresh ctx a scratch sized for this batch alone would stay the ctx's --
+    // launch_canon allocates the default only when there is none -- and a later device batch would find its long records refused)
+    if (worst_case_dw(max_len) > TIER_D_DW) {
+        const uint64_t want = worst_case_dw(max_len) * 4;
+        if ((rc = ensure_gscratch(c, want < c->gscratch_default ? c->gscratch_default : want))) return rc;
+    }
     // The batch goes through the device in PARTS of >= 16 MB (up to sixteen): part k + 1 is copied in while part k - 1 is copied
     // out on a stream of the ctx's own; with page-locked buffers (circkit_host_alloc) the two directions of the link work at
     // the same time.  One part = the round-2 behaviour: in, compute, out, one after the other

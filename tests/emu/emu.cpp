@@ -140,7 +140,7 @@ void run_wave(void (*body)(void*), void* arg) { run_block(body, arg, 1); }
 #include "../../circkit_amd/csrc/xxh3_core.h"
 
 namespace {
-struct Launch { ck::CanonArgs a; uint32_t* lds; const uint32_t* lut; const uint32_t* lutn = nullptr; const uint32_t* lean_lutn = nullptr; uint32_t* blk_count; uint32_t block, nblocks, wib; bool all_records = false, alpha = false, solo = true; const uint32_t* htab = nullptr; };
+struct Launch { ck::CanonArgs a; uint32_t* lds; const uint32_t* lut; const uint32_t* lutn = nullptr; const uint32_t* lean_lutn = nullptr; uint32_t* blk_count; uint32_t block, nblocks, wib; bool all_records = false, alpha = false, solo = true, team4 = true; const uint32_t* htab = nullptr; };
 void mixed_body(void* p)         // one fiber of a 4-wave workgroup of canon_mixed[_n][_h]_kernel (NM = the batch's MODE_ALPHA, HASH = out_hash given)
 {
     Launch* L = (Launch*)p;
@@ -165,7 +165,7 @@ void wave_body(void* p)          // one fiber of a 4-wave workgroup of the LDS t
     const uint32_t wib = ck::emu::cur_wave();
     ck::canon_wave_loop(L->a, L->lds + wib * L->a.slice_dw, L->lut, L->blk_count, L->block, L->nblocks, wib, 4, L->lutn);
     ck::block_barrier();
-    ck::team_pass(L->a, L->lds, L->lut, L->lutn, L->blk_count, L->block, wib, 4, L->solo);
+    ck::team_pass(L->a, L->lds, L->lut, L->lutn, L->blk_count, L->block, wib, 4, L->solo, L->team4);
 }
 void rescue_body(void* p)
 {
@@ -314,6 +314,67 @@ extern "C" int emu_canonicalize_batch(const uint8_t* bytes, const uint64_t* offs
         }
     }
     if (n_fused_hash) { *n_fused_hash = 0; for (uint64_t r = 0; r < n_records; ++r) *n_fused_hash += hashed[r]; }
+    return (int)status;
+}
+
+// LDS footprint of ONE 4-wave workgroup at a given slice size (tests/tier_sets.py): kind 0 = a tier workgroup (wave_body) over
+// the list `list` (entries with their flag bits, dealt wib, wib + 4, ...), kind 1 / 2 = a workgroup of the mixed-length kernel's
+// pure / N build (mixed_body) over all records.  The LDS is filled with `pattern`; behind the four slices lies a guard of
+// FOOTPRINT_GUARD_DW dwords, and only behind the guard the deferral counter with the team's words and the tables -- so a write past
+// a slice lands in the next slice or in the guard, where nothing else writes.  high_water[w]: dwords of slice w from its start
+// to the last one that no longer holds the pattern (0: untouched); *guard_touched: guard dwords that changed.
+// opts: bit 0 = the team pass's wave-0-alone fallback, bit 1 = its 4-bit team (canon_kernel<4, true>).
+// deferred[0 .. *n_deferred): the workgroup's output segment, flag bits included.  Returns status[0].
+constexpr uint32_t FOOTPRINT_GUARD_DW = 256;
+extern "C" int emu_tier_footprint(const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records, const uint32_t* list, uint32_t n_list,
+                                  uint8_t* out_bytes, uint32_t* out_index, uint8_t* out_strand, uint32_t* out_view, uint32_t slice_dw, int kind,
+                                  uint32_t opts, uint32_t flags, uint32_t pattern, uint32_t* high_water, uint32_t* guard_touched,
+                                  uint32_t* deferred, uint32_t* n_deferred)
+{
+    if (kind < 0 || kind > 2) return -1;
+    uint8_t comp[256];
+    for (int v = 0; v < 256; ++v) comp[v] = (uint8_t)v;
+    const char *x = "AGCTYRWSKMDVHBN", *y = "TCGARYWSMKHBDVN";
+    for (int i = 0; x[i]; ++i) { comp[(uint8_t)x[i]] = y[i]; comp[(uint8_t)x[i] + 32] = y[i] + 32; }
+    const size_t guard0 = (size_t)4 * slice_dw, behind = guard0 + FOOTPRINT_GUARD_DW;
+    std::vector<uint32_t> lds(behind + 4 + ck::FAST_LUT_DW + ck::FAST_LUTN_DW + ck::LEAN_LUTN_DW, pattern);
+    uint32_t* blk = lds.data() + behind;
+    uint32_t* lut = blk + 4;
+    uint32_t* lutn = lut + ck::FAST_LUT_DW;
+    uint32_t* lean_lutn = lutn + ck::FAST_LUTN_DW;
+    blk[0] = blk[1] = blk[2] = blk[3] = 0;
+    ck::fast_lut_init(lut, 0, 1);
+    ck::fast_lutn_init(lutn, 0, 1);
+    ck::lean_lutn_init(lean_lutn, 0, 1);
+    const uint32_t cap = (uint32_t)(kind == 0 ? n_list : n_records) + 4;
+    std::vector<uint32_t> seg(cap, 0);
+    uint32_t status = 0, count_in = n_list, count_out = 0;
+    Launch L;
+    L.a = ck::CanonArgs{};
+    L.a.bytes = bytes; L.a.offsets = offsets; L.a.n_records = n_records;
+    L.a.out_bytes = out_bytes; L.a.out_index = out_index; L.a.out_strand = out_strand; L.a.out_view = out_view;
+    L.a.status = &status; L.a.comp_lut = comp; L.a.flags = flags; L.a.slice_dw = slice_dw;
+    L.a.defer_list = seg.data(); L.a.defer_count = &count_out; L.a.out_seg_cap = cap;
+    L.lds = lds.data(); L.lut = lut; L.lutn = lutn; L.lean_lutn = lean_lutn; L.blk_count = blk; L.block = 0; L.nblocks = 1;
+    L.solo = (opts & 1) != 0; L.team4 = (opts & 2) != 0; L.alpha = kind == 2;
+    if (kind == 0) {
+        L.a.list = list; L.a.list_count = &count_in; L.a.in_nseg = 1; L.a.in_seg_cap = n_list ? n_list : 1; L.a.segs_per_block = 1;
+        ck::emu::run_block(wave_body, &L, 4);
+    } else {
+        L.a.all_seg_cap = (uint32_t)n_records;                     // one segment: records 0 .. n_records - 1, record i to wave i % 4
+        ck::emu::run_block(mixed_body, &L, 4);
+    }
+    for (uint32_t w = 0; w < 4; ++w) {
+        uint32_t hw = 0;
+        for (uint32_t k = slice_dw; k > 0; --k)
+            if (lds[(size_t)w * slice_dw + k - 1] != pattern) { hw = k; break; }
+        high_water[w] = hw;
+    }
+    uint32_t g = 0;
+    for (uint32_t k = 0; k < FOOTPRINT_GUARD_DW; ++k) g += lds[guard0 + k] != pattern;
+    *guard_touched = g;
+    *n_deferred = blk[0];
+    for (uint32_t k = 0; k < blk[0]; ++k) deferred[k] = seg[k];
     return (int)status;
 }
 

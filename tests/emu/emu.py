@@ -114,3 +114,51 @@ def xxh3_64(b):
     _lib.emu_xxh3_64.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     buf = ctypes.create_string_buffer(bytes(b) + b"\0" * 16, len(b) + 16)
     return int(_lib.emu_xxh3_64(ctypes.addressof(buf), len(b)))
+
+
+FOOTPRINT_PATTERN = 0xC5A7D1E3          # what an untouched LDS dword holds in tier_footprint()
+FOOTPRINT_GUARD_DW = 256
+S_OUT, S_IDX, S_STRAND = 0x3F, 0xFFFFFFFF, 0xFF
+
+
+def tier_footprint(data, offsets, slice_dw, kind="tier", entries=None, solo=True, team4=True, flags=0, want_bytes=True, want_index=True,
+                   want_strand=True, base_shift=0):
+    """One 4-wave workgroup with its LDS pre-filled with FOOTPRINT_PATTERN and a guard region behind the four slices
+    (emu_tier_footprint).  kind "tier": canon_kernel<4>'s loop and team pass over the list `entries` (record indices, flag bits
+    allowed; entry i is wave i % 4's); "mixed" / "mixed_n": the mixed-length kernel's pure / N build over all records (record i is
+    wave i % 4's).  Returns bytes (0x3F where nothing was written), index, strand, high_water (per wave slice: dwords from the
+    slice's start to the last one that changed), guard_touched, deferred (the output segment's entries) and status."""
+    global _lib
+    if _lib is None:
+        canonicalize_batch(np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64))
+    fn = _lib.emu_tier_footprint
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4 + \
+        [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    assert offsets[0] == 0
+    raw = np.full(64 + base_shift + len(data) + 64, 0x4E, dtype=np.uint8)
+    skew = (-raw.ctypes.data) % 64 + base_shift         # payload pointer = 64-byte boundary + base_shift
+    pad = raw[skew:]
+    pad[:len(data)] = data
+    inp = raw.copy()
+    raw_out = np.full(len(raw), S_OUT, dtype=np.uint8)
+    out = raw_out[skew:]
+    idx = np.full(n + 64, S_IDX, dtype=np.uint32)
+    strand = np.full(n + 64, S_STRAND, dtype=np.uint8)
+    ent = np.ascontiguousarray(entries if entries is not None else [], dtype=np.uint32)
+    hw = np.zeros(4, dtype=np.uint32)
+    guard = ctypes.c_uint32(0)
+    deferred = np.zeros(max(len(ent), n) + 4, dtype=np.uint32)
+    ndef = ctypes.c_uint32(0)
+    st = fn(pad.ctypes.data, offsets.ctypes.data, n, ent.ctypes.data if len(ent) else None, len(ent), out.ctypes.data if want_bytes else None,
+            idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None, None, int(slice_dw),
+            {"tier": 0, "mixed": 1, "mixed_n": 2}[kind], int(bool(solo)) | (2 if team4 else 0), int(flags), FOOTPRINT_PATTERN, hw.ctypes.data,
+            ctypes.byref(guard), deferred.ctypes.data, ctypes.byref(ndef))
+    assert st >= 0
+    assert (out[len(data):] == S_OUT).all() and (raw_out[:skew] == S_OUT).all(), "kernel wrote outside the batch"
+    assert (idx[n:] == S_IDX).all() and (strand[n:] == S_STRAND).all(), "kernel wrote a per-record output past record n - 1"
+    assert np.array_equal(raw, inp), "kernel wrote into its input"
+    return dict(bytes=out[:len(data)].copy(), index=idx[:n], strand=strand[:n], high_water=[int(x) for x in hw], guard_touched=guard.value,
+                deferred=[int(x) for x in deferred[:ndef.value]], status=st)
