@@ -72,6 +72,9 @@ SIGNATURES = {
     "circkit_fasta_parse_device": (_i, [_vp, _vp, _u64, _i, _i, _vp, _u64, _vp, _u64, _vp, _vp]),
     "circkit_fasta_parse_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 3),
     "circkit_fasta_parse_text": (_i, [_vp, _vp, _u64, _i, _i, _vp, _u64, _vp, _u64, _vp, _vp] + [ctypes.POINTER(_u64)] * 3),
+    "circkit_fasta_write_device": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "circkit_fasta_write_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "circkit_fasta_write_text": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
     "circkit_synth_fill_device": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "circkit_fixed_offsets_device": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "circkit_bench_copy_device": (_i, [_vp, _vp, _vp, _u64, _u32]),
@@ -565,6 +568,69 @@ class Context:
         recs = [(text[int(head[i][0]):int(head[i][0] + head[i][1])], text[int(raw[i][0]):int(raw[i][0] + raw[i][1])]) for i in range(r.value)]
         return recs, data, offs, used.value
 
+    # -- FASTA text from the device ------------------------------------------------------------------
+    def fasta_write_device(self, d_text, n_text, d_head, n_heads, n_out, d_out_text, out_capacity, d_out_offsets, d_body=None,
+                           d_body_offsets=None, d_raw=None, d_src=None, n_src=None, d_labels=None):
+        """Enqueues circkit_fasta_write_device: output record k = '>' head label '\\n' body '\\n' into
+        d_out_text[d_out_offsets[k] .. d_out_offsets[k + 1]).  d_head / d_raw: the spans of fasta_parse_device; d_src (n_src
+        entries): a compact's d_out_src; d_labels: the windows of orfs_windows_device; the body is d_body / d_body_offsets (a CSR
+        batch of n_out records) or the raw spans.  fasta_write_status() waits and returns the totals."""
+        self._check(self._lib.circkit_fasta_write_device(self._h, _ptr(d_text), int(n_text), _ptr(d_head), _ptr(d_raw), int(n_heads), _ptr(d_src),
+                                                         int(n_heads if n_src is None else n_src), _ptr(d_labels), _ptr(d_body), _ptr(d_body_offsets),
+                                                         int(n_out), _ptr(d_out_text), int(out_capacity), _ptr(d_out_offsets)))
+
+    def fasta_write_status(self):
+        """Waits for the last FASTA write; returns (total bytes, invalid records).  Raises CirckitError: OOM when the total
+        exceeded the capacity, INVALID_ARG when the output overlapped an input or records were invalid."""
+        t, bad = _u64(0), _u64(0)
+        self._check(self._lib.circkit_fasta_write_status(self._h, ctypes.byref(t), ctypes.byref(bad)))
+        return t.value, bad.value
+
+    def fasta_write_text(self, text, head, body=None, offsets=None, raw=None, src=None, labels=None):
+        """FASTA text of host arrays, written on the device (circkit_fasta_write_text): (bytes, out_offsets).  text: the input
+        text the spans point into; head / raw: (R, 2) uint64 arrays of (off, len) or FASTA_SPAN_DTYPE; body / offsets: a CSR
+        batch, one record per output; src: the kept-record map; labels: an array of WINDOW_DTYPE.  Exactly one of body (with
+        offsets) and raw.  Grows its buffer to the reported total and runs again; invalid records raise CirckitError."""
+        text = bytes(text)
+        buf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        head = np.ascontiguousarray(head).view(np.uint64).reshape(-1, 2)
+        n_heads = len(head)
+        if (body is None) != (offsets is None) or (body is None) == (raw is None):
+            raise ValueError("exactly one of body (with offsets) and raw must be given")
+        if raw is not None:
+            raw = np.ascontiguousarray(raw).view(np.uint64).reshape(-1, 2)
+            if len(raw) != n_heads:
+                raise ValueError("head and raw must have one span per record each")
+        if src is not None:
+            src = np.ascontiguousarray(src, dtype=np.uint64)
+        n_src = n_heads if src is None else len(src)
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=WINDOW_DTYPE)
+        if body is not None:
+            body = np.ascontiguousarray(body, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if len(offsets) < 1 or int(offsets[-1]) > len(body):
+                raise ValueError("offsets must end inside body")
+            if not len(body):
+                body = np.zeros(1, dtype=np.uint8)
+        n_out = len(offsets) - 1 if offsets is not None else len(labels) if labels is not None else n_src
+        if labels is not None and len(labels) != n_out:
+            raise ValueError("one label per output record")
+        out_off = np.zeros(n_out + 1, dtype=np.uint64)
+        cap = max(len(text) + (len(body) if body is not None else 0), 1)
+        while True:
+            out = np.empty(cap, dtype=np.uint8)
+            total = _u64(0)
+            rc = self._lib.circkit_fasta_write_text(self._h, _ptr(buf) if text else None, len(text), _ptr(head) if n_heads else None,
+                                                    _ptr(raw) if raw is not None else None, n_heads, _ptr(src) if src is not None else None, n_src,
+                                                    _ptr(labels) if labels is not None else None, _ptr(body), _ptr(offsets), n_out, _ptr(out), cap,
+                                                    _ptr(out_off), ctypes.byref(total))
+            if rc == -5 and cap < total.value < 2 ** 64 - 1:      # grow to the reported total and run again
+                cap = total.value
+                continue
+            self._check(rc)
+            return out[:total.value].tobytes(), out_off
+
     # -- cyclic windows ------------------------------------------------------------------------
     def windows_gather_device(self, d_bytes, d_offsets, n_records, d_windows, n_windows, d_out_bytes, out_capacity, d_out_offsets):
         """Enqueues circkit_windows_gather_device: window k of d_windows (WINDOW_DTYPE, device) packed into
@@ -976,6 +1042,11 @@ def orf_proteins(data, offsets, include_stop=False, **kw):
 def fasta_parse_gpu(text, first_chunk=True, final_chunk=True, keep_on_device=False):
     """fasta_parse with the parse on the GPU (Context.fasta_parse_text): the same four results."""
     return default_context().fasta_parse_text(text, first_chunk=first_chunk, final_chunk=final_chunk, keep_on_device=keep_on_device)
+
+
+def fasta_write_gpu(text, head, **kw):
+    """FASTA text written on the GPU (Context.fasta_write_text): (bytes, out_offsets)."""
+    return default_context().fasta_write_text(text, head, **kw)
 
 
 def fasta_parse(text, first_chunk=True, final_chunk=True):

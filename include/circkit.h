@@ -533,6 +533,47 @@ int circkit_fasta_parse_text(circkit_ctx* ctx, const uint8_t* text, uint64_t n_t
                              circkit_fasta_span* head, circkit_fasta_span* raw, uint64_t* n_records, uint64_t* payload_bytes,
                              uint64_t* consumed);
 
+/* ---- FASTA text from the device ------------------------------------------------------------------ */
+/* The inverse of circkit_fasta_parse_device: what every command of the reference writes (src/canonicalize.rs:33-37,
+ * src/uniq.rs:50-61, src/orfs.rs:111-122,144-152, src/rotate.rs, src/concatenate.rs, src/monomerize.rs), packed back to back.
+ * Output record k =  '>'  head_k  label_k  '\n'  body_k  '\n'
+ *   i_k     = d_labels ? d_labels[k].record : k                       (must be < n_src)
+ *   h_k     = d_src ? d_src[i_k] : i_k                                (must be < n_heads; with d_src null, n_src == n_heads)
+ *   head_k  = d_text[d_head[h_k].off .. + d_head[h_k].len)
+ *   label_k = d_labels ? (strand ? "_RC_ORF" : "_ORF") + decimal(d_labels[k].start) : nothing     (src/orfs.rs:113-114,146-147)
+ *   body_k  = d_body ? d_body[d_body_offsets[k] .. d_body_offsets[k+1]) : d_text[d_raw[h_k].off .. + d_raw[h_k].len)
+ * exactly one of d_body (with d_body_offsets, uint64[n_out + 1]) and d_raw is given.  d_head / d_raw are the spans of
+ * circkit_fasta_parse_device, d_src the d_out_src of either compact, d_labels what circkit_orfs_windows_device writes (the
+ * array that cuts the ORF sequences or proteins labels them; its `length` is not read).  The number is the u32 in plain decimal,
+ * 1 to 10 digits; there is no line wrapping.
+ * Device pointers; the call only enqueues work on the ctx stream.  No pointer but the 8-byte arrays needs any alignment; neither
+ * the text nor the body is written.  d_out_offsets (uint64[n_out + 1], [0] = 0) is always written in full; lengths add up
+ * saturating (a total that does not fit 64 bits is UINT64_MAX, which no capacity holds).  When the total exceeds out_capacity,
+ * or [d_out_text, d_out_text + total) overlaps the text or the body payload d_body[d_body_offsets[0] .. d_body_offsets[n_out])
+ * (the offsets are the device's, so the device decides), no byte of d_out_text is written.  A record is INVALID when
+ * i_k >= n_src, h_k >= n_heads, its head or raw span does not lie in [0, n_text) (off > n_text or len > n_text - off), its label
+ * has strand > 1 or reserved != 0, or its body range decreases or leaves the payload: it is counted and written as zero bytes,
+ * and nothing it names is dereferenced.  Null / non-null combinations that make no sense (both or neither of d_body and d_raw,
+ * d_body without d_body_offsets, null d_out_offsets, null d_out_text with a capacity, null d_src with n_src != n_heads), or
+ * n_text > 2^40, or n_heads, n_src or n_out >= 2^40: INVALID_ARG, nothing enqueued.  n_out == 0 is valid. */
+int circkit_fasta_write_device(circkit_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const circkit_fasta_span* d_head,
+                               const circkit_fasta_span* d_raw, uint64_t n_heads, const uint64_t* d_src, uint64_t n_src,
+                               const circkit_window* d_labels, const uint8_t* d_body, const uint64_t* d_body_offsets,
+                               uint64_t n_out, uint8_t* d_out_text, uint64_t out_capacity, uint64_t* d_out_offsets);
+/* Waits for the most recent write of this ctx (device or host form): *total_bytes = out_offsets[n_out], *n_invalid = its invalid
+ * records.  CIRCKIT_ERR_OOM when the total exceeded the capacity, CIRCKIT_ERR_INVALID_ARG when the output overlapped an input
+ * or n_invalid != 0 (with n_invalid != 0 and nothing else wrong the valid records ARE written).  The totals are the write's
+ * own: circkit_fasta_parse_status, circkit_windows_status and circkit_translate_status answer for their kind as before. */
+int circkit_fasta_write_status(circkit_ctx* ctx, uint64_t* total_bytes, uint64_t* n_invalid);
+/* circkit_fasta_write_device with HOST buffers; synchronizes.  out_offsets (n_out + 1) and *total are always written; when
+ * *total > out_capacity nothing is written to out_text and the call returns CIRCKIT_ERR_OOM, so that the caller can grow its
+ * buffer and call again.  Invalid records: CIRCKIT_ERR_INVALID_ARG after the valid ones were written.  body_offsets must not
+ * decrease; body[0 .. body_offsets[n_out]) is copied in.  The staging is the ctx's and only grows. */
+int circkit_fasta_write_text(circkit_ctx* ctx, const uint8_t* text, uint64_t n_text, const circkit_fasta_span* head,
+                             const circkit_fasta_span* raw, uint64_t n_heads, const uint64_t* src, uint64_t n_src,
+                             const circkit_window* labels, const uint8_t* body, const uint64_t* body_offsets, uint64_t n_out,
+                             uint8_t* out_text, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total);
+
 /* ---- synthetic input on the device (bench / tests) ------------------------------ */
 /* Fills d_bytes[0..n_bases) with uniform ACGT from the counter-based generator keyed by
  * (seed, first_base + i) -- the same bytes oracle/ck_oracle_synth_fill produces on the host. */
