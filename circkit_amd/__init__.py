@@ -5,10 +5,10 @@ api.py     ctypes mirror of the reference's lib-crate API over that C ABI
 monomerize.py  `circkit monomerize` over the GPU batch call (also `python -m circkit_amd.monomerize`); the module is
            callable: circkit_amd.monomerize(s, ...) is Monomerizer::monomerize on one record
 """
-from .api import (GENETIC_CODES, CirckitError, Context, canonicalize, cat_batch, decat_batch, default_context, fasta_parse_gpu, fasta_write_gpu, find_orfs,  # noqa: F401
+from .api import (GENETIC_CODES, SKETCH_EMPTY, CirckitError, Context, canonicalize, cat_batch, decat_batch, default_context, fasta_parse_gpu, fasta_write_gpu, find_orfs,  # noqa: F401
                   lmsr,
                   lmsr_index, load_library, monomer_end_index, monomer_filter, monomerize_params, monomers_batch, normalize, orf_params,
-                  orf_proteins, orf_sequences, revcomp_batch, rotate_batch, translate_params, uniq_batch, windows_translate, xxh3_64)
+                  orf_proteins, orf_sequences, revcomp_batch, rotate_batch, sketch_batch, sketch_params, sketch_similarity, translate_params, uniq_batch, windows_translate, xxh3_64)
 from . import uniq  # noqa: F401,E402
 
 

@@ -97,6 +97,12 @@ SIGNATURES = {
     "circkit_windows_translate_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
     "circkit_translate_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "circkit_windows_translate": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
+    "circkit_sketch_batch_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "circkit_sketch_status": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u32)]),
+    "circkit_sketch_compare_device": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _u64, _vp]),
+    "circkit_sketch_compare_status": (_i, [_vp, ctypes.POINTER(_u64)]),
+    "circkit_sketch_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "circkit_sketch_compare": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _u64, _vp]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -133,6 +139,22 @@ def translate_params(table=1, unknown="X", first_as_m=False):
     for k, v in enumerate(aa):
         p.aa[k] = v
     p.unknown, p.first_as_m = unk[0], int(bool(first_as_m))
+    return p
+
+
+# circkit_sketch_params / CIRCKIT_SKETCH_EMPTY (include/circkit.h)
+SKETCH_EMPTY = 0xFFFFFFFFFFFFFFFF
+
+
+class SketchParams(ctypes.Structure):
+    _fields_ = [("k", _u32), ("log2_bins", _u32), ("seed", _u64), ("reserved", _u32 * 2)]
+
+
+def sketch_params(k=21, log2_bins=8, seed=0):
+    """circkit_sketch_params from Python values: k-mers of k symbols (4 .. 32), 1 << log2_bins bins (log2_bins 4 .. 10), the seed
+    xor-ed into every canonical k-mer before it is hashed.  The library checks the ranges."""
+    p = SketchParams()
+    p.k, p.log2_bins, p.seed = int(k), int(log2_bins), int(seed) & SKETCH_EMPTY
     return p
 
 
@@ -716,6 +738,63 @@ class Context:
             self._check(rc)
             return out[:total.value], out_off
 
+    # -- sketches of circular records ---------------------------------------------------------------
+    def sketch_batch_device(self, d_bytes, d_offsets, n_records, d_out_sketch, d_out_n_kmers=None, params=None, **kw):
+        """Enqueues circkit_sketch_batch_device: row i of d_out_sketch (uint64[n_records << log2_bins], device) = the cyclic k-mer
+        MinHash sketch of record i, d_out_n_kmers[i] (uint32, optional) its valid k-mers.  params: a sketch_params() result, or
+        its keywords.  sketch_status() waits and returns the totals."""
+        p = params if params is not None else sketch_params(**kw)
+        self._check(self._lib.circkit_sketch_batch_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), ctypes.byref(p),
+                                                          _ptr(d_out_sketch), _ptr(d_out_n_kmers)))
+
+    def sketch_status(self):
+        """Waits for the last sketch; returns (valid k-mers of all records, records of 2^31 symbols or more).  Raises CirckitError
+        (TOO_LONG) when the latter is not 0."""
+        t, bad = _u64(0), _u32(0)
+        self._check(self._lib.circkit_sketch_status(self._h, ctypes.byref(t), ctypes.byref(bad)))
+        return t.value, bad.value
+
+    def sketch_compare_device(self, d_sketch_a, n_a, d_sketch_b, n_b, log2_bins, d_pairs, n_pairs, d_out):
+        """Enqueues circkit_sketch_compare_device: d_out[2p], d_out[2p + 1] = (match, filled) of row d_pairs[2p] of d_sketch_a and
+        row d_pairs[2p + 1] of d_sketch_b (uint32, device).  sketch_compare_status() waits."""
+        self._check(self._lib.circkit_sketch_compare_device(self._h, _ptr(d_sketch_a), int(n_a), _ptr(d_sketch_b), int(n_b), int(log2_bins),
+                                                            _ptr(d_pairs), int(n_pairs), _ptr(d_out)))
+
+    def sketch_compare_status(self):
+        """Waits for the last compare; returns its invalid pairs (0), or raises CirckitError (INVALID_ARG) when there were any."""
+        bad = _u64(0)
+        self._check(self._lib.circkit_sketch_compare_status(self._h, ctypes.byref(bad)))
+        return bad.value
+
+    def sketch_batch(self, data, offsets, params=None, **kw):
+        """The sketches of a host CSR batch: (rows, n_kmers) with rows an (n, 1 << log2_bins) uint64 array.  params or the keywords
+        of sketch_params."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        p = params if params is not None else sketch_params(**kw)
+        n = len(offsets) - 1
+        bins = 1 << p.log2_bins if 0 <= p.log2_bins < 32 else 1
+        rows = np.empty((n, bins), dtype=np.uint64)
+        counts = np.empty(n, dtype=np.uint32)
+        self._check(self._lib.circkit_sketch_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, ctypes.byref(p),
+                                                   _ptr(rows) if n else None, _ptr(counts) if n else None))
+        return rows, counts
+
+    def sketch_compare(self, sk_a, sk_b, pairs):
+        """(match, filled) of every pair (i, j): row i of sk_a against row j of sk_b, host arrays of one bin count.  sk_b may be
+        sk_a itself.  Invalid pairs raise CirckitError after the valid ones were computed."""
+        same = sk_b is sk_a
+        sk_a = np.ascontiguousarray(sk_a, dtype=np.uint64)
+        sk_b = sk_a if same else np.ascontiguousarray(sk_b, dtype=np.uint64)
+        if sk_a.ndim != 2 or sk_b.ndim != 2 or sk_a.shape[1] != sk_b.shape[1] or sk_a.shape[1] & (sk_a.shape[1] - 1) or not sk_a.shape[1]:
+            raise ValueError("sketches are (n, bins) arrays of one power-of-two bin count")
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        m = len(pairs)
+        out = np.zeros((m, 2), dtype=np.uint32)
+        self._check(self._lib.circkit_sketch_compare(self._h, _ptr(sk_a), len(sk_a), _ptr(sk_b), len(sk_b), sk_a.shape[1].bit_length() - 1,
+                                                     _ptr(pairs) if m else None, m, _ptr(out) if m else None))
+        return out[:, 0].copy(), out[:, 1].copy()
+
     def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
         """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
         import torch
@@ -1033,6 +1112,22 @@ def orf_sequences(data, offsets, include_stop=False, **orf_params):
 
 def windows_translate(data, offsets, windows, **kw):
     return default_context().windows_translate(data, offsets, windows, **kw)
+
+
+def sketch_batch(seqs, k=21, log2_bins=8, seed=0):
+    """The cyclic k-mer MinHash sketches of a list of normalized records (bytes): an (n, 1 << log2_bins) uint64 array, rotation-
+    and strand-invariant row by row, and the records' valid k-mer counts."""
+    seqs = [bytes(s) for s in seqs]
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    data = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    return default_context().sketch_batch(data, offsets, k=k, log2_bins=log2_bins, seed=seed)
+
+
+def sketch_similarity(sk_a, sk_b, pairs):
+    """(match, filled) of every pair (i, j) of rows of two sketch arrays: match / filled estimates the Jaccard index of the two
+    records' canonical cyclic k-mer sets."""
+    return default_context().sketch_compare(sk_a, sk_b, pairs)
 
 
 def orf_proteins(data, offsets, include_stop=False, **kw):

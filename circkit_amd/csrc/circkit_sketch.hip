@@ -1,0 +1,323 @@
+// circkit_sketch.hip -- MinHash sketches of circular records and their comparison: the "sketches of circular records" section of
+// include/circkit.h.  The routines are sketch.h's; here are the kernels around them, the unit's state and the ABI.
+//
+// A sketch is two launches on the ctx stream, nothing waits and no workgroup waits for another:
+//   sketch_short_kernel   one wave per record (striding): the row and count of a record of up to SKETCH_SEG symbols; a longer one gets
+//                         an EMPTY row and count 0 and is appended to the ctx's list, or counted as unprocessed from 2^31 symbols on
+//   sketch_long_kernel    a fixed grid over that list: the spans of every long record, merged into its row by the global minimum
+// A compare is one launch: sketch_compare_kernel, one wave per pair (striding).
+// The LDS of the first two is sized at the launch: SKETCH_WAVES slices of sketch.h's lds_words(log2_bins) 64-bit words.
+// The totals of either kind are the unit's own: they stay in device memory and are copied to page-locked memory behind the work,
+// and circkit_sketch_status / circkit_sketch_compare_status answer from them whatever other unit ran in between.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/circkit.h"
+#include "ck_ctx.h"
+#include "sketch.h"
+
+using ck_sketch::Compare;
+using ck_sketch::Sketch;
+using ck_sketch::SKETCH_WAVES;
+using ck_sketch::T_WORDS;
+
+static_assert(sizeof(circkit_sketch_params) == 24, "params layout");
+static_assert(CIRCKIT_SKETCH_EMPTY == ck_sketch::EMPTY, "the header's EMPTY is the routines'");
+
+namespace {
+
+constexpr uint32_t SHORT_MAX_GRID = 8192;              // workgroups of the short kernel: 8 per CU and SIMD's worth, striding over the records
+constexpr uint32_t LONG_GRID = 2048;                   // workgroups of the long kernel
+constexpr uint32_t COMPARE_WAVES = 4, COMPARE_MAX_GRID = 1u << 16;
+
+__global__ __launch_bounds__(64 * SKETCH_WAVES) void sketch_short_kernel(Sketch S)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t sketch_lds[];
+    ck_sketch::short_block(S, sketch_lds, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64 * SKETCH_WAVES) void sketch_long_kernel(Sketch S)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t sketch_lds[];
+    ck_sketch::long_block(S, sketch_lds, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64 * COMPARE_WAVES) void sketch_compare_kernel(Compare C)
+{
+    ck_sketch::compare_wave(C, (uint64_t)blockIdx.x * COMPARE_WAVES + ck::wave_in_block(), (uint64_t)gridDim.x * COMPARE_WAVES);
+}
+
+struct SketchState {
+    uint64_t* d_totals = nullptr;    // [T_WORDS]
+    uint64_t* h_totals = nullptr;    // the same, page-locked: valid once the ctx stream has run past the copy
+    uint64_t* d_invalid = nullptr;   // the invalid pairs of the most recent compare
+    uint64_t* h_invalid = nullptr;
+    bool any = false, any_compare = false;
+    uint64_t* d_long = nullptr; uint64_t cap_long = 0;          // the list of long records (grow only, n_records entries)
+    // the staging of the host forms (grow only)
+    uint8_t* d_bytes = nullptr; uint64_t cap_bytes = 0;
+    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
+    uint64_t* d_rows = nullptr; uint64_t cap_rows = 0;
+    uint32_t* d_counts = nullptr; uint64_t cap_counts = 0;
+    uint64_t* d_rows_b = nullptr; uint64_t cap_rows_b = 0;
+    uint32_t* d_pairs = nullptr; uint64_t cap_pairs = 0;
+    uint32_t* d_result = nullptr; uint64_t cap_result = 0;
+};
+
+void release_state(void* p)
+{
+    SketchState* S = (SketchState*)p;
+    if (!S) return;
+    void* ptrs[] = { S->d_totals, S->d_invalid, S->d_long, S->d_bytes, S->d_off, S->d_rows, S->d_counts, S->d_rows_b, S->d_pairs, S->d_result };
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    if (S->h_invalid) (void)hipHostFree(S->h_invalid);
+    delete S;
+}
+
+int state(circkit_ctx* c, SketchState** out)
+{
+    void** slot = ck_ctx_slot(c, CK_UNIT_SKETCH, release_state);
+    if (!*slot) *slot = new SketchState();
+    SketchState* S = (SketchState*)*slot;
+    *out = S;
+    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
+    if (!S->d_invalid) CK_HIP(c, hipMalloc((void**)&S->d_invalid, sizeof(uint64_t)));
+    if (!S->h_totals) {
+        CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+        for (int k = 0; k < T_WORDS; ++k) S->h_totals[k] = 0;
+    }
+    if (!S->h_invalid) {
+        CK_HIP(c, hipHostMalloc((void**)&S->h_invalid, sizeof(uint64_t), hipHostMallocDefault));
+        *S->h_invalid = 0;
+    }
+    return CIRCKIT_OK;
+}
+
+template <typename T>
+int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
+{
+    if (want <= *cap) return CIRCKIT_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
+    *cap = want;
+    return CIRCKIT_OK;
+}
+
+bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+int check_params(circkit_ctx* c, const circkit_sketch_params* p)
+{
+    if (!p) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null sketch params");
+    if (p->k < ck_sketch::K_MIN || p->k > ck_sketch::K_MAX) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "k must be 4 .. 32");
+    if (p->log2_bins < ck_sketch::LOG2_BINS_MIN || p->log2_bins > ck_sketch::LOG2_BINS_MAX)
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "log2_bins must be 4 .. 10");
+    if (p->reserved[0] || p->reserved[1]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "the reserved words of circkit_sketch_params must be 0");
+    return CIRCKIT_OK;
+}
+
+// the two launches and the copy of the totals; the arguments are checked
+int launch_sketch(circkit_ctx* c, SketchState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const circkit_sketch_params& p,
+                  uint64_t* d_out, uint32_t* d_counts)
+{
+    int rc;
+    if ((rc = grow(c, &S->d_long, &S->cap_long, n ? n : 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    if (n) {
+        Sketch K;
+        K.bytes = d_bytes; K.offsets = d_offsets; K.n_records = n;
+        K.k = p.k; K.log2_bins = p.log2_bins; K.seed = p.seed;
+        K.out = d_out; K.out_count = d_counts;
+        K.long_list = S->d_long; K.totals = S->d_totals;
+        const uint64_t blocks = (n + SKETCH_WAVES - 1) / SKETCH_WAVES;
+        const size_t lds = (size_t)SKETCH_WAVES * ck_sketch::lds_words(p.log2_bins) * sizeof(uint64_t);
+        hipLaunchKernelGGL(sketch_short_kernel, dim3((uint32_t)(blocks > SHORT_MAX_GRID ? SHORT_MAX_GRID : blocks)), dim3(64 * SKETCH_WAVES), lds, st, K);
+        hipLaunchKernelGGL(sketch_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), lds, st, K);
+        CK_HIP(c, hipGetLastError());
+    }
+    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    S->any = true;
+    return CIRCKIT_OK;
+}
+
+int check_totals(circkit_ctx* c, const uint64_t* t)
+{
+    if (t[ck_sketch::T_UNPROCESSED])
+        return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "%llu records of 2^31 symbols or more were not sketched: their rows are empty",
+                       (unsigned long long)t[ck_sketch::T_UNPROCESSED]);
+    return CIRCKIT_OK;
+}
+
+int launch_compare(circkit_ctx* c, SketchState* S, const uint64_t* d_a, uint64_t n_a, const uint64_t* d_b, uint64_t n_b, uint32_t log2_bins,
+                   const uint32_t* d_pairs, uint64_t n_pairs, uint32_t* d_out)
+{
+    hipStream_t st = ck_ctx_stream(c);
+    CK_HIP(c, hipMemsetAsync(S->d_invalid, 0, sizeof(uint64_t), st));
+    if (n_pairs) {
+        Compare C;
+        C.a = d_a; C.b = d_b; C.n_a = n_a; C.n_b = n_b;
+        C.log2_bins = log2_bins;
+        C.pairs = d_pairs; C.n_pairs = n_pairs;
+        C.out = d_out; C.n_invalid = S->d_invalid;
+        const uint64_t blocks = (n_pairs + COMPARE_WAVES - 1) / COMPARE_WAVES;
+        hipLaunchKernelGGL(sketch_compare_kernel, dim3((uint32_t)(blocks > COMPARE_MAX_GRID ? COMPARE_MAX_GRID : blocks)), dim3(64 * COMPARE_WAVES), 0, st, C);
+        CK_HIP(c, hipGetLastError());
+    }
+    CK_HIP(c, hipMemcpyAsync(S->h_invalid, S->d_invalid, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    S->any_compare = true;
+    return CIRCKIT_OK;
+}
+
+int check_invalid(circkit_ctx* c, uint64_t n_invalid)
+{
+    if (n_invalid) return ck_fail(c, CIRCKIT_ERR_INVALID_ARG, "%llu invalid pairs were written as (0, 0)", (unsigned long long)n_invalid);
+    return CIRCKIT_OK;
+}
+
+int check_compare_args(circkit_ctx* c, const void* a, const void* b, uint32_t log2_bins, const void* pairs, uint64_t n_pairs, const void* out)
+{
+    if (log2_bins < ck_sketch::LOG2_BINS_MIN || log2_bins > ck_sketch::LOG2_BINS_MAX)
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "log2_bins must be 4 .. 10");
+    if (n_pairs && (!a || !b || !pairs || !out)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_pairs >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_pairs too large");
+    return CIRCKIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int circkit_sketch_batch_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records, const circkit_sketch_params* params,
+                                uint64_t* d_out_sketch, uint32_t* d_out_n_kmers)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_params(c, params))) return rc;
+    if (n_records && (!d_bytes || !d_offsets || !d_out_sketch)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (((uintptr_t)d_out_sketch & 7u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_out_n_kmers & 3u))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_offsets and d_out_sketch must be 8-byte aligned, d_out_n_kmers 4-byte aligned");
+    if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
+    // the arrays whose extent the host knows; the payload's ends are the device's, and keeping the outputs off it is the caller's contract
+    const uint64_t row_bytes = (n_records << params->log2_bins) * sizeof(uint64_t);
+    if (overlap(d_out_sketch, row_bytes, d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
+        overlap(d_out_n_kmers, n_records * sizeof(uint32_t), d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
+        overlap(d_out_sketch, row_bytes, d_out_n_kmers, n_records * sizeof(uint32_t)))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_sketch / d_out_n_kmers overlap the offsets or each other");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    SketchState* S;
+    if ((rc = state(c, &S))) return rc;
+    return launch_sketch(c, S, d_bytes, d_offsets, n_records, *params, d_out_sketch, d_out_n_kmers);
+}
+
+int circkit_sketch_status(circkit_ctx* c, uint64_t* n_valid_kmers_total, uint32_t* n_unprocessed)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    SketchState* S;
+    int rc;
+    if ((rc = state(c, &S))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    const uint64_t none[T_WORDS] = { 0, 0, 0 };
+    const uint64_t* t = S->any ? S->h_totals : none;
+    if (n_valid_kmers_total) *n_valid_kmers_total = t[ck_sketch::T_VALID];
+    if (n_unprocessed) *n_unprocessed = t[ck_sketch::T_UNPROCESSED] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t[ck_sketch::T_UNPROCESSED];
+    return check_totals(c, t);
+}
+
+int circkit_sketch_compare_device(circkit_ctx* c, const uint64_t* d_sketch_a, uint64_t n_a, const uint64_t* d_sketch_b, uint64_t n_b, uint32_t log2_bins,
+                                  const uint32_t* d_pairs, uint64_t n_pairs, uint32_t* d_out)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_compare_args(c, d_sketch_a, d_sketch_b, log2_bins, d_pairs, n_pairs, d_out))) return rc;
+    if (((uintptr_t)d_sketch_a & 7u) || ((uintptr_t)d_sketch_b & 7u) || ((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_out & 3u))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "the sketches must be 8-byte aligned, d_pairs and d_out 4-byte aligned");
+    const uint64_t out_bytes = n_pairs * 2 * sizeof(uint32_t);
+    if (overlap(d_out, out_bytes, d_pairs, out_bytes) || overlap(d_out, out_bytes, d_sketch_a, (n_a << log2_bins) * sizeof(uint64_t)) ||
+        overlap(d_out, out_bytes, d_sketch_b, (n_b << log2_bins) * sizeof(uint64_t)))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out overlaps the pairs or a sketch");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    SketchState* S;
+    if ((rc = state(c, &S))) return rc;
+    return launch_compare(c, S, d_sketch_a, n_a, d_sketch_b, n_b, log2_bins, d_pairs, n_pairs, d_out);
+}
+
+int circkit_sketch_compare_status(circkit_ctx* c, uint64_t* n_invalid)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    SketchState* S;
+    int rc;
+    if ((rc = state(c, &S))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
+    const uint64_t bad = S->any_compare ? *S->h_invalid : 0;
+    if (n_invalid) *n_invalid = bad;
+    return check_invalid(c, bad);
+}
+
+int circkit_sketch_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records, const circkit_sketch_params* params,
+                         uint64_t* out_sketch, uint32_t* out_n_kmers)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_params(c, params))) return rc;
+    if (n_records && (!offsets || !out_sketch)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
+    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
+    // from the offsets alone, before a payload byte is read
+    for (uint64_t i = 0; i < n_records; ++i) {
+        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+        if (offsets[i + 1] - offsets[i] >= ck_sketch::TOO_LONG)
+            return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was sketched", (unsigned long long)i);
+    }
+    const uint64_t nb = n_records ? offsets[n_records] : 0;
+    if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    SketchState* S;
+    if ((rc = state(c, &S))) return rc;
+    const uint64_t n_rows = n_records << params->log2_bins;
+    if ((rc = grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
+    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
+    if ((rc = grow(c, &S->d_counts, &S->cap_counts, n_records ? n_records : 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
+    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if ((rc = launch_sketch(c, S, S->d_bytes, S->d_off, n_records, *params, S->d_rows, S->d_counts))) return rc;
+    if (n_rows) CK_HIP(c, hipMemcpyAsync(out_sketch, S->d_rows, n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (n_records && out_n_kmers) CK_HIP(c, hipMemcpyAsync(out_n_kmers, S->d_counts, n_records * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
+    return check_totals(c, S->h_totals);
+}
+
+int circkit_sketch_compare(circkit_ctx* c, const uint64_t* sketch_a, uint64_t n_a, const uint64_t* sketch_b, uint64_t n_b, uint32_t log2_bins,
+                           const uint32_t* pairs, uint64_t n_pairs, uint32_t* out)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_compare_args(c, sketch_a, sketch_b, log2_bins, pairs, n_pairs, out))) return rc;
+    if (n_a >= (1ull << 40) || n_b >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_a or n_b too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    SketchState* S;
+    if ((rc = state(c, &S))) return rc;
+    const bool same = sketch_a == sketch_b;
+    const uint64_t wa = (same && n_b > n_a ? n_b : n_a) << log2_bins, wb = same ? 0 : n_b << log2_bins;
+    if ((rc = grow(c, &S->d_rows, &S->cap_rows, wa ? wa : 1))) return rc;
+    if ((rc = grow(c, &S->d_rows_b, &S->cap_rows_b, wb ? wb : 1))) return rc;
+    if ((rc = grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
+    if ((rc = grow(c, &S->d_result, &S->cap_result, n_pairs ? 2 * n_pairs : 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    if (n_pairs && wa) CK_HIP(c, hipMemcpyAsync(S->d_rows, sketch_a, wa * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_pairs && wb) CK_HIP(c, hipMemcpyAsync(S->d_rows_b, sketch_b, wb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_pairs) CK_HIP(c, hipMemcpyAsync(S->d_pairs, pairs, 2 * n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if ((rc = launch_compare(c, S, S->d_rows, n_a, same ? S->d_rows : S->d_rows_b, n_b, log2_bins, S->d_pairs, n_pairs, S->d_result))) return rc;
+    if (n_pairs) CK_HIP(c, hipMemcpyAsync(out, S->d_result, 2 * n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CK_HIP(c, hipStreamSynchronize(st));
+    return check_invalid(c, *S->h_invalid);
+}
+
+}  // extern "C"

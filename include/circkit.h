@@ -483,6 +483,69 @@ int circkit_windows_translate(circkit_ctx* ctx, const uint8_t* bytes, const uint
                               const circkit_window* windows, uint64_t n_windows, const circkit_translate_params* params,
                               uint8_t* out_aa, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total);
 
+/* ---- sketches of circular records ---------------------------------------------------------------- */
+/* Nothing in the reference is replaced: its roadmap names `cluster` and `prealign` as the next commands, and both need a cheap
+ * similarity between circular records that depends neither on where a record was cut nor on the strand read.  This section is
+ * the definition.  A record of n symbols (n < 2^31) has, when n >= k, the n cyclic k-mers of the symbols (p + i) mod n,
+ * i = 0..k-1, one per start p; when n < k it has none.  A k-mer is VALID when its k bytes are all of A C G T (upper case: the
+ * batches are normalized; lower case, N, '-' and anything else make it invalid, and it is skipped).  f = the k-mer packed to 2k
+ * bits with A, C, G, T = 0..3, first symbol most significant; r = the same packing of its reverse complement; c = min(f, r);
+ *   h = fmix64(c ^ seed),  fmix64 = MurmurHash3's finalizer:  h ^= h >> 33; h *= 0xff51afd7ed558ccd; h ^= h >> 33;
+ *                                                             h *= 0xc4ceb9fe1a85ec53; h ^= h >> 33
+ * The record's sketch is a row of s = 1 << log2_bins words: row[b] = the minimum h over the valid k-mers with
+ * h >> (64 - log2_bins) == b, CIRCKIT_SKETCH_EMPTY where there is none (the one k-mer in 2^64 whose h is 2^64 - 1 is, by
+ * definition, indistinguishable from an empty bin).  n_kmers = the number of valid k-mers, that one included.  The row is a
+ * function of the multiset of canonical cyclic k-mers: bit-identical for every rotation of the record, for its reverse
+ * complement, and (n >= k) for the record twice in a row. */
+typedef struct circkit_sketch_params {
+    uint32_t k;                              /* 4 .. 32 */
+    uint32_t log2_bins;                      /* 4 .. 10: 16 .. 1024 bins */
+    uint64_t seed;
+    uint32_t reserved[2];                    /* 0 */
+} circkit_sketch_params;
+#define CIRCKIT_SKETCH_EMPTY 0xFFFFFFFFFFFFFFFFull
+
+/* The sketch of every record of a batch (no counterpart in the reference: its roadmap's `cluster` / `prealign`).  Device
+ * pointers; the call only enqueues work on the ctx stream.  offsets[0] need not be 0; d_bytes needs no alignment.
+ *   d_out_sketch   uint64[n_records << log2_bins], 8-byte aligned: row i = record i's; every row is written in full, the rows
+ *                  of records with n < k (all EMPTY) included
+ *   d_out_n_kmers  uint32[n_records] or null: the valid k-mers of every record
+ * A record of 2^31 symbols or more is not dereferenced: it gets an all-EMPTY row and count 0, and is counted
+ * (circkit_sketch_status).  The outputs must not overlap the inputs: against the offsets and each other the host checks
+ * (INVALID_ARG); the payload's extent is the device's, and keeping the outputs off it is the caller's contract.  k, log2_bins
+ * out of range, reserved != 0, null params or null buffers with records: INVALID_ARG, nothing enqueued.  n_records == 0 is
+ * valid.  The result is bit-identical from run to run. */
+int circkit_sketch_batch_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                const circkit_sketch_params* params, uint64_t* d_out_sketch, uint32_t* d_out_n_kmers);
+/* Waits for the most recent sketch of this ctx (device or host form; no counterpart in the reference, roadmap `cluster`):
+ * *n_valid_kmers_total = the valid k-mers of all records, *n_unprocessed = the records of 2^31 symbols or more;
+ * CIRCKIT_ERR_TOO_LONG when n_unprocessed != 0.  The totals are the sketch's own: this call answers for the most recent sketch
+ * whatever other unit ran in between, as circkit_fasta_write_status does for its kind. */
+int circkit_sketch_status(circkit_ctx* ctx, uint64_t* n_valid_kmers_total, uint32_t* n_unprocessed);
+/* Compares rows of two sketch arrays over a list of pairs (no counterpart in the reference, roadmap `cluster` / `prealign`).
+ * Pair p = (i, j) = d_pairs[2p], d_pairs[2p + 1]: i indexes d_sketch_a (n_a rows), j indexes d_sketch_b (n_b rows), rows of
+ * 1 << log2_bins words; the two arrays may be the same pointer.  d_out[2p] = match = the bins with A[b] == B[b] != EMPTY,
+ * d_out[2p + 1] = filled = the bins with A[b] != EMPTY or B[b] != EMPTY.  match / filled is the one-permutation-hashing estimate
+ * of the Jaccard index of the two k-mer sets; the caller divides.  A pair with i >= n_a or j >= n_b is INVALID: it is written
+ * as (0, 0) and counted, and nothing it names is dereferenced.  Device pointers (the sketches 8-byte, the pairs and d_out
+ * 4-byte aligned); the call only enqueues.  log2_bins out of range, null buffers with pairs, or d_out overlapping an input:
+ * INVALID_ARG, nothing enqueued.  n_pairs == 0 is valid. */
+int circkit_sketch_compare_device(circkit_ctx* ctx, const uint64_t* d_sketch_a, uint64_t n_a, const uint64_t* d_sketch_b,
+                                  uint64_t n_b, uint32_t log2_bins, const uint32_t* d_pairs, uint64_t n_pairs, uint32_t* d_out);
+/* Waits for the most recent compare of this ctx (device or host form; roadmap `cluster`, nothing replaced): *n_invalid = its
+ * invalid pairs; CIRCKIT_ERR_INVALID_ARG when there was any, after the valid pairs were written. */
+int circkit_sketch_compare_status(circkit_ctx* ctx, uint64_t* n_invalid);
+/* circkit_sketch_batch_device with HOST buffers (roadmap `cluster`, nothing replaced): copies the batch in, sketches, copies the
+ * rows and counts (out_n_kmers may be null) home and synchronizes.  offsets[0] must be 0 and the offsets must not decrease; a
+ * record of 2^31 symbols or more is refused from the offsets alone, before anything is read: CIRCKIT_ERR_TOO_LONG, nothing
+ * computed.  The staging is the ctx's and only grows. */
+int circkit_sketch_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                         const circkit_sketch_params* params, uint64_t* out_sketch, uint32_t* out_n_kmers);
+/* circkit_sketch_compare_device with HOST buffers (roadmap `cluster`, nothing replaced): copies the rows and pairs in, compares,
+ * copies the results home and synchronizes; invalid pairs: CIRCKIT_ERR_INVALID_ARG after the valid ones were written. */
+int circkit_sketch_compare(circkit_ctx* ctx, const uint64_t* sketch_a, uint64_t n_a, const uint64_t* sketch_b, uint64_t n_b,
+                           uint32_t log2_bins, const uint32_t* pairs, uint64_t n_pairs, uint32_t* out);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
