@@ -158,10 +158,12 @@ def cyclic_cut(src, start, n):
     if n <= 0 or not src:
         return b""
     s = start % len(src)
-    out = src[s:s + n]
-    while len(out) < n:
-        out += src[:n - len(out)]
-    return out
+    parts = [src[s:s + n]]                                 # (collected and joined once: a window of half a million laps stays linear)
+    have = len(parts[0])
+    while have < n:
+        parts.append(src[:n - have])
+        have += len(parts[-1])
+    return src[:0].join(parts)
 
 
 def cli_orfs(data, min_length=75, start_codons="ATG", stop_codons="TAA,TAG,TGA", include_stop=False, no_stop_required=False,
