@@ -17,6 +17,7 @@
 
 #include "../../include/circkit.h"
 #include "ck_ctx.h"
+#include "ck_scan.h"
 #include "fasta_device.h"
 #include "fasta_host.h"
 
@@ -83,38 +84,12 @@ __global__ __launch_bounds__(ck_fasta::WG) void fasta_summaries_kernel(const uin
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_fasta::summarize_tile(T, t, S, &summaries[t]);
 }
 
-// exclusive scans over the workgroup: of the state (the last event wins) and of a sum
-__device__ inline uint32_t block_scan_state(uint32_t v, uint32_t* lds, uint32_t* last)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < SCAN_WG; d <<= 1) {
-        const uint32_t prev = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] = ck_fasta::next_state(prev, lds[threadIdx.x]);
-        __syncthreads();
-    }
-    const uint32_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0;
-    *last = lds[SCAN_WG - 1];
-    __syncthreads();
-    return before;
-}
-
-__device__ inline uint64_t block_scan_sum(uint64_t v, uint64_t* lds, uint64_t* total)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < SCAN_WG; d <<= 1) {
-        const uint64_t add = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const uint64_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0;
-    *total = lds[SCAN_WG - 1];
-    __syncthreads();
-    return before;
-}
+// the scan of the state (ck_scan.h): the last event wins, ST_PASS hands the state on
+struct StateOp {
+    typedef uint32_t T;
+    CK_DEV T identity() { return ck_fasta::ST_PASS; }
+    CK_DEV T combine(T earlier, T later) { return ck_fasta::next_state(earlier, later); }
+};
 
 // One workgroup.  A round takes SCAN_WG summaries: the state in front of each tile first, which decides what the tile keeps,
 // then the sums of records and bytes (one word: a round's records stay below 2^24, its bytes below 2^32).  The next round's
@@ -136,9 +111,10 @@ __global__ __launch_bounds__(SCAN_WG) void fasta_scan_kernel(const Summary* __re
         const Summary s = next;
         next = idx + SCAN_WG < n_tiles ? summaries[idx + SCAN_WG] : none;
         uint32_t last;
-        const uint32_t in = ck_fasta::next_state(state, block_scan_state(s.kind, lds_state, &last));
+        const uint32_t in = ck_fasta::next_state(state, ck_scan::block_scan<SCAN_WG, StateOp>(threadIdx.x, s.kind, lds_state, &last));
         uint64_t total;
-        const uint64_t before = block_scan_sum((uint64_t)s.starts << 32 | ck_fasta::tile_kept(s, in), lds_sum, &total);
+        const uint64_t before = ck_scan::block_scan<SCAN_WG, ck_scan::Add>(threadIdx.x, (uint64_t)s.starts << 32 | ck_fasta::tile_kept(s, in), lds_sum,
+                                                                         &total);
         if (idx < n_tiles) prefix[idx] = Prefix{ records + (before >> 32), bytes + (before & 0xFFFFFFFFull), in };
         state = ck_fasta::next_state(state, last);
         records += total >> 32;
@@ -188,8 +164,7 @@ __global__ __launch_bounds__(SPANS_WG) void fasta_spans_kernel(const uint8_t* __
 
 struct FastaState {
     uint8_t* d_lut = nullptr;        // ckhost::normalize_lut(), copied when the slot is made
-    uint64_t* d_totals = nullptr;    // [T_WORDS]
-    uint64_t* h_totals = nullptr;    // the same, page-locked: valid once the ctx stream has run past the copy
+    ck_totals totals;                // [T_WORDS], made with the state
     uint64_t byte_capacity = 0, record_capacity = 0;       // of the most recent parse, for the status message
     bool any = false;
     Summary* d_summaries = nullptr; uint64_t cap_summaries = 0;
@@ -207,9 +182,9 @@ void release_state(void* p)
 {
     FastaState* S = (FastaState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_lut, S->d_totals, S->d_summaries, S->d_prefix, S->d_spare, S->d_text, S->d_out, S->d_off, S->d_head, S->d_raw };
+    void* ptrs[] = { S->d_lut, S->d_summaries, S->d_prefix, S->d_spare, S->d_text, S->d_out, S->d_off, S->d_head, S->d_raw };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    ck_totals_release(&S->totals);
     delete S;
 }
 
@@ -226,22 +201,7 @@ int state(circkit_ctx* c, FastaState** out)
         if (e != hipSuccess) { (void)hipFree(lut); CK_HIP(c, e); }
         S->d_lut = lut;
     }
-    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
-    if (!S->h_totals) {
-        CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
-        for (int k = 0; k < T_WORDS; ++k) S->h_totals[k] = 0;
-    }
-    return CIRCKIT_OK;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
+    return ck_totals_make(c, &S->totals, T_WORDS);
 }
 
 // no text of n bytes holds more records than this: a record is at least ">\n", the last one at least ">"
@@ -252,37 +212,37 @@ int launch_parse(circkit_ctx* c, FastaState* S, const uint8_t* d_text, uint64_t 
 {
     const uint64_t tiles = (n + ck_fasta::TILE_BYTES - 1) / ck_fasta::TILE_BYTES;
     int rc;
-    if ((rc = grow(c, &S->d_summaries, &S->cap_summaries, tiles ? tiles : 1))) return rc;
-    if ((rc = grow(c, &S->d_prefix, &S->cap_prefix, tiles ? tiles : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_summaries, &S->cap_summaries, tiles ? tiles : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_prefix, &S->cap_prefix, tiles ? tiles : 1))) return rc;
     if ((d_head != nullptr) != (d_raw != nullptr)) {
         const uint64_t most = most_records(n), spare = record_capacity < most ? record_capacity : most;
-        if ((rc = grow(c, &S->d_spare, &S->cap_spare, spare ? spare : 1))) return rc;
+        if ((rc = ck_grow(c, &S->d_spare, &S->cap_spare, spare ? spare : 1))) return rc;
         if (!d_head) d_head = S->d_spare; else d_raw = S->d_spare;
     }
     const uint32_t flags = (first_chunk ? FLAG_FIRST : 0) | (final_chunk ? FLAG_FINAL : 0);
     const uint32_t grid = (uint32_t)(tiles < FASTA_GRID ? tiles : FASTA_GRID);
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    if ((rc = ck_totals_clear(c, &S->totals, T_WORDS))) return rc;
     if (tiles) {
-        hipLaunchKernelGGL(fasta_bounds_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, S->d_totals);
-        hipLaunchKernelGGL(fasta_summaries_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, flags, (const uint64_t*)S->d_totals,
+        hipLaunchKernelGGL(fasta_bounds_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, S->totals.d);
+        hipLaunchKernelGGL(fasta_summaries_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, flags, (const uint64_t*)S->totals.d,
                            (const uint8_t*)S->d_lut, S->d_summaries, tiles);
     }
     hipLaunchKernelGGL(fasta_scan_kernel, dim3(1), dim3(SCAN_WG), 0, st, (const Summary*)S->d_summaries, tiles, S->d_prefix, d_text, n, flags,
-                       (const uint8_t*)d_out, byte_capacity, record_capacity, d_offsets, S->d_totals);
+                       (const uint8_t*)d_out, byte_capacity, record_capacity, d_offsets, S->totals.d);
     if (tiles) {
-        hipLaunchKernelGGL(fasta_apply_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, flags, (const uint64_t*)S->d_totals,
+        hipLaunchKernelGGL(fasta_apply_kernel, dim3(grid), dim3(ck_fasta::WG), 0, st, d_text, n, flags, (const uint64_t*)S->totals.d,
                            (const uint8_t*)S->d_lut, (const Prefix*)S->d_prefix, tiles, d_out, d_offsets, d_head, d_raw);
         if (d_head) {
             const uint64_t most = most_records(n), upto = record_capacity < most ? record_capacity : most;
             const uint64_t want = (upto + SPANS_WG - 1) / SPANS_WG;
             if (want)
                 hipLaunchKernelGGL(fasta_spans_kernel, dim3((uint32_t)(want < SPANS_MAX_GRID ? want : SPANS_MAX_GRID)), dim3(SPANS_WG), 0, st, d_text, n,
-                                   flags, (const uint64_t*)S->d_totals, d_head, d_raw);
+                                   flags, (const uint64_t*)S->totals.d, d_head, d_raw);
         }
     }
     CK_HIP(c, hipGetLastError());
-    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
     S->byte_capacity = byte_capacity;
     S->record_capacity = record_capacity;
     S->any = true;
@@ -329,7 +289,7 @@ int circkit_fasta_parse_status(circkit_ctx* c, uint64_t* n_records, uint64_t* pa
     if ((rc = state(c, &S))) return rc;
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t none[T_WORDS] = { 0 };
-    const uint64_t* t = S->any ? S->h_totals : none;
+    const uint64_t* t = S->any ? S->totals.h : none;
     const bool format = t[T_REFUSED] == ck_fasta::REFUSED_FORMAT;
     if (n_records) *n_records = format ? 0 : t[T_RECORDS];
     if (payload_bytes) *payload_bytes = format ? 0 : t[T_BYTES];
@@ -351,11 +311,11 @@ int circkit_fasta_parse_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     // no text needs more than this, whatever the caller's buffers hold
     const uint64_t most = most_records(n_text);
     const uint64_t bytes_cap = byte_capacity < n_text ? byte_capacity : n_text, records_cap = record_capacity < most ? record_capacity : most;
-    if ((rc = grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
-    if ((rc = grow(c, &S->d_out, &S->cap_out, bytes_cap ? bytes_cap : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, records_cap + 1))) return rc;
-    if (head && (rc = grow(c, &S->d_head, &S->cap_head, records_cap ? records_cap : 1))) return rc;
-    if (raw && (rc = grow(c, &S->d_raw, &S->cap_raw, records_cap ? records_cap : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, bytes_cap ? bytes_cap : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, records_cap + 1))) return rc;
+    if (head && (rc = ck_grow(c, &S->d_head, &S->cap_head, records_cap ? records_cap : 1))) return rc;
+    if (raw && (rc = ck_grow(c, &S->d_raw, &S->cap_raw, records_cap ? records_cap : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (n_text) CK_HIP(c, hipMemcpyAsync(S->d_text, text, n_text, hipMemcpyHostToDevice, st));
     if ((rc = launch_parse(c, S, S->d_text, n_text, first_chunk, final_chunk, S->d_out, bytes_cap, S->d_off, records_cap, head ? S->d_head : nullptr,
@@ -364,7 +324,7 @@ int circkit_fasta_parse_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     S->byte_capacity = byte_capacity;
     S->record_capacity = record_capacity;
     CK_HIP(c, hipStreamSynchronize(st));
-    const uint64_t* t = S->h_totals;
+    const uint64_t* t = S->totals.h;
     const bool format = t[T_REFUSED] == ck_fasta::REFUSED_FORMAT;
     const uint64_t R = format ? 0 : t[T_RECORDS], B = format ? 0 : t[T_BYTES];
     if (n_records) *n_records = R;

@@ -9,8 +9,8 @@
 //                            comparison with the capacity and the refusal of an output that overlaps the text or the body
 //   fwrite_apply_kernel      out_offsets in place: the lengths become the offsets
 //   fwrite_write_kernel      write_tile over the output tiles, unless the scan refused the write
-// The scan has the shape of circkit_windows.hip's (which stays as it is: its kernels take a window list); the sums saturate, so
-// out_offsets never decreases.  The totals are this unit's own: they stay in device memory and are copied to page-locked memory
+// The three scan kernels are ck_scan.h's bodies with fasta_write.h's SCAN_WG, SCAN_ITEMS and the saturating sum, so out_offsets
+// never decreases.  The totals are this unit's own: they stay in device memory and are copied to page-locked memory
 // behind the write, and circkit_fasta_write_status answers from them whatever parse, gather or translate ran in between.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +18,7 @@
 
 #include "../../include/circkit.h"
 #include "ck_ctx.h"
+#include "ck_scan.h"
 #include "fasta_write.h"
 
 using ck_fwrite::Label;
@@ -54,30 +55,10 @@ __global__ __launch_bounds__(LEN_WG) void fwrite_lengths_kernel(Source src, uint
     }
 }
 
-// exclusive scan over the workgroup, saturating; *total = the workgroup's sum
-__device__ inline uint64_t block_scan(uint64_t v, uint64_t* lds, uint64_t* total)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < SCAN_WG; d <<= 1) {
-        const uint64_t add = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] = ck_fwrite::sat_add(lds[threadIdx.x], add);
-        __syncthreads();
-    }
-    const uint64_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0;
-    *total = lds[SCAN_WG - 1];
-    __syncthreads();
-    return before;
-}
-
 __global__ __launch_bounds__(SCAN_WG) void fwrite_tile_sums_kernel(const uint64_t* __restrict__ len, uint64_t m, uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v = 0, total;
-    for (int k = 0; k < SCAN_ITEMS; ++k) if (t0 + k < m) v = ck_fwrite::sat_add(v, len[t0 + k]);
-    block_scan(v, lds, &total);
+    const uint64_t total = ck_scan::tile_sum<SCAN_WG, SCAN_ITEMS, ck_scan::SatAdd>(threadIdx.x, blockIdx.x, len, m, [](uint64_t w) { return w; }, lds);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -86,18 +67,11 @@ __global__ __launch_bounds__(SCAN_WG) void fwrite_scan_sums_kernel(uint64_t* __r
                                                                    uint64_t capacity, uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ totals)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < n_tiles; b += SCAN_WG) {
-        const uint64_t idx = b + threadIdx.x;
-        uint64_t chunk;
-        const uint64_t before = block_scan(idx < n_tiles ? sums[idx] : 0, lds, &chunk);
-        if (idx < n_tiles) sums[idx] = ck_fwrite::sat_add(carry, before);
-        carry = ck_fwrite::sat_add(carry, chunk);
-    }
+    const uint64_t total = ck_scan::sums_exclusive<SCAN_WG, ck_scan::SatAdd>(threadIdx.x, sums, n_tiles, lds);
     if (threadIdx.x == 0) {
         const Source S = with_payload(src, m);
-        totals[T_TOTAL] = carry;
-        totals[T_REFUSED] = ck_fwrite::verdict(carry, capacity, S.text, S.n_text, S.body, S.b0, S.b1, out);
+        totals[T_TOTAL] = total;
+        totals[T_REFUSED] = ck_fwrite::verdict(total, capacity, S.text, S.n_text, S.body, S.b0, S.b1, out);
         out_offsets[0] = 0;
     }
 }
@@ -106,15 +80,7 @@ __global__ __launch_bounds__(SCAN_WG) void fwrite_scan_sums_kernel(uint64_t* __r
 __global__ __launch_bounds__(SCAN_WG) void fwrite_apply_kernel(uint64_t* __restrict__ ends, uint64_t m, const uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t loc[SCAN_ITEMS];
-    uint64_t v = 0, total;
-    for (int k = 0; k < SCAN_ITEMS; ++k) { loc[k] = t0 + k < m ? ends[t0 + k] : 0; v = ck_fwrite::sat_add(v, loc[k]); }
-    uint64_t run = ck_fwrite::sat_add(sums[blockIdx.x], block_scan(v, lds, &total));
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        run = ck_fwrite::sat_add(run, loc[k]);
-        if (t0 + k < m) ends[t0 + k] = run;
-    }
+    ck_scan::apply_ends<SCAN_WG, SCAN_ITEMS, ck_scan::SatAdd>(threadIdx.x, blockIdx.x, ends, m, sums, lds);
 }
 
 __global__ __launch_bounds__(64 * ck_fwrite::WRITE_WAVES) void fwrite_write_kernel(Source src, uint64_t m, const uint64_t* __restrict__ out_offsets,
@@ -133,8 +99,7 @@ __global__ __launch_bounds__(64 * ck_fwrite::WRITE_WAVES) void fwrite_write_kern
 }
 
 struct WriteState {
-    uint64_t* d_totals = nullptr;    // [T_WORDS]
-    uint64_t* h_totals = nullptr;    // the same, page-locked: valid once the ctx stream has run past the copy
+    ck_totals totals;                // [T_WORDS], made with the state
     uint64_t capacity = 0;           // of the most recent write, for the status message
     bool any = false;
     uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
@@ -154,9 +119,9 @@ void release_state(void* p)
 {
     WriteState* S = (WriteState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_totals, S->d_sums, S->d_text, S->d_head, S->d_raw, S->d_src, S->d_labels, S->d_body, S->d_body_off, S->d_out_off, S->d_out };
+    void* ptrs[] = { S->d_sums, S->d_text, S->d_head, S->d_raw, S->d_src, S->d_labels, S->d_body, S->d_body_off, S->d_out_off, S->d_out };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_totals) (void)hipHostFree(S->h_totals);
+    ck_totals_release(&S->totals);
     delete S;
 }
 
@@ -166,22 +131,7 @@ int state(circkit_ctx* c, WriteState** out)
     if (!*slot) *slot = new WriteState();
     WriteState* S = (WriteState*)*slot;
     *out = S;
-    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
-    if (!S->h_totals) {
-        CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
-        for (int k = 0; k < T_WORDS; ++k) S->h_totals[k] = 0;
-    }
-    return CIRCKIT_OK;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
+    return ck_totals_make(c, &S->totals, T_WORDS);
 }
 
 // what both forms refuse before anything is enqueued
@@ -204,16 +154,16 @@ int launch_offsets(circkit_ctx* c, WriteState* S, const Source& src, uint64_t m,
 {
     const uint64_t tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
     int rc;
-    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    if ((rc = ck_totals_clear(c, &S->totals, T_WORDS))) return rc;
     if (m) {
         const uint64_t grid = (m + LEN_WG - 1) / LEN_WG;
         hipLaunchKernelGGL(fwrite_lengths_kernel, dim3((uint32_t)(grid > LEN_MAX_GRID ? LEN_MAX_GRID : grid)), dim3(LEN_WG), 0, st, src, m, d_out_offsets,
-                           S->d_totals);
+                           S->totals.d);
         hipLaunchKernelGGL(fwrite_tile_sums_kernel, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_out_offsets + 1, m, S->d_sums);
     }
-    hipLaunchKernelGGL(fwrite_scan_sums_kernel, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles, src, m, d_out, capacity, d_out_offsets, S->d_totals);
+    hipLaunchKernelGGL(fwrite_scan_sums_kernel, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles, src, m, d_out, capacity, d_out_offsets, S->totals.d);
     if (m) hipLaunchKernelGGL(fwrite_apply_kernel, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, d_out_offsets + 1, m, (const uint64_t*)S->d_sums);
     CK_HIP(c, hipGetLastError());
     S->capacity = capacity;
@@ -225,14 +175,8 @@ int launch_write(circkit_ctx* c, WriteState* S, const Source& src, uint64_t m, c
 {
     if (!m || !d_out) return CIRCKIT_OK;               // no record writes a byte
     hipLaunchKernelGGL(fwrite_write_kernel, dim3(WRITE_GRID), dim3(64 * ck_fwrite::WRITE_WAVES), 0, ck_ctx_stream(c), src, m, d_out_offsets,
-                       (const uint64_t*)S->d_totals, d_out);
+                       (const uint64_t*)S->totals.d, d_out);
     CK_HIP(c, hipGetLastError());
-    return CIRCKIT_OK;
-}
-
-int copy_totals(circkit_ctx* c, WriteState* S)
-{
-    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
     return CIRCKIT_OK;
 }
 
@@ -278,7 +222,7 @@ int circkit_fasta_write_device(circkit_ctx* c, const uint8_t* d_text, uint64_t n
     const Source src = source_of(d_text, n_text, d_head, d_raw, n_heads, d_src, n_src, d_labels, d_body, d_body_offsets);
     if ((rc = launch_offsets(c, S, src, n_out, d_out_text, out_capacity, d_out_offsets))) return rc;
     if ((rc = launch_write(c, S, src, n_out, d_out_offsets, d_out_text))) return rc;
-    return copy_totals(c, S);
+    return ck_totals_fetch(c, &S->totals, T_WORDS);
 }
 
 int circkit_fasta_write_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* n_invalid)
@@ -289,7 +233,7 @@ int circkit_fasta_write_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* 
     if ((rc = state(c, &S))) return rc;
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t none[T_WORDS] = { 0, 0, 0 };
-    const uint64_t* t = S->any ? S->h_totals : none;
+    const uint64_t* t = S->any ? S->totals.h : none;
     if (total_bytes) *total_bytes = t[T_TOTAL];
     if (n_invalid) *n_invalid = t[T_INVALID];
     return check_totals(c, t, S->capacity);
@@ -314,14 +258,14 @@ int circkit_fasta_write_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     WriteState* S;
     if ((rc = state(c, &S))) return rc;
-    if ((rc = grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
-    if ((rc = grow(c, &S->d_head, &S->cap_head, n_heads ? n_heads : 1))) return rc;
-    if (raw && (rc = grow(c, &S->d_raw, &S->cap_raw, n_heads ? n_heads : 1))) return rc;
-    if (src && (rc = grow(c, &S->d_src, &S->cap_src, n_src ? n_src : 1))) return rc;
-    if (labels && (rc = grow(c, &S->d_labels, &S->cap_labels, n_out ? n_out : 1))) return rc;
-    if (body && (rc = grow(c, &S->d_body, &S->cap_body, nb ? nb : 1))) return rc;
-    if (body && (rc = grow(c, &S->d_body_off, &S->cap_body_off, n_out + 1))) return rc;
-    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n_out + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_head, &S->cap_head, n_heads ? n_heads : 1))) return rc;
+    if (raw && (rc = ck_grow(c, &S->d_raw, &S->cap_raw, n_heads ? n_heads : 1))) return rc;
+    if (src && (rc = ck_grow(c, &S->d_src, &S->cap_src, n_src ? n_src : 1))) return rc;
+    if (labels && (rc = ck_grow(c, &S->d_labels, &S->cap_labels, n_out ? n_out : 1))) return rc;
+    if (body && (rc = ck_grow(c, &S->d_body, &S->cap_body, nb ? nb : 1))) return rc;
+    if (body && (rc = ck_grow(c, &S->d_body_off, &S->cap_body_off, n_out + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_out + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (n_text) CK_HIP(c, hipMemcpyAsync(S->d_text, text, n_text, hipMemcpyHostToDevice, st));
     if (n_heads && head) CK_HIP(c, hipMemcpyAsync(S->d_head, head, n_heads * sizeof(Span), hipMemcpyHostToDevice, st));
@@ -335,20 +279,20 @@ int circkit_fasta_write_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
                                  body ? S->d_body_off : nullptr);
     // the offsets first: the staging for the text is sized by the total they end in (it cannot overlap the staged inputs)
     if ((rc = launch_offsets(c, S, dev, n_out, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = copy_totals(c, S))) return rc;
+    if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
     CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_out + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
-    const uint64_t B = S->h_totals[T_TOTAL];
+    const uint64_t B = S->totals.h[T_TOTAL];
     if (total) *total = B;
-    if (S->h_totals[T_REFUSED]) return check_totals(c, S->h_totals, out_capacity);
+    if (S->totals.h[T_REFUSED]) return check_totals(c, S->totals.h, out_capacity);
     if (B) {
         if (!out_text) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
         if ((rc = launch_write(c, S, dev, n_out, S->d_out_off, S->d_out))) return rc;
         CK_HIP(c, hipMemcpyAsync(out_text, S->d_out, B, hipMemcpyDeviceToHost, st));
         CK_HIP(c, hipStreamSynchronize(st));
     }
-    return check_totals(c, S->h_totals, out_capacity);
+    return check_totals(c, S->totals.h, out_capacity);
 }
 
 }  // extern "C"

@@ -7,8 +7,8 @@
 // the batch with CIRCKIT_ERR_TOO_LONG.
 //
 // Compact (the writer closure on the device, monomer_compact.h): compact_decide_kernel applies the writer's filters, one lane
-// per record; three scan kernels turn (written, written length) into each written record's slot and byte offset and the two
-// totals; compact_gather_kernel packs the monomers, by output bytes.  All five are enqueued back to back: the totals stay in
+// per record; three scan kernels (ck_scan.h's bodies over PairAdd) turn (written, written length) into each written record's
+// slot and byte offset and the two totals; compact_gather_kernel packs the monomers, by output bytes.  All five are enqueued back to back: the totals stay in
 // ctx-owned device memory, which is why the gather runs a fixed grid that strides over however many tiles there turn out to be.
 // Everything behind the decide kernel knows a record only by its word w[i], and is open to the other units through
 // ck_compact_launch.h: circkit_uniq_compact.hip fills w from uniq's first_seen and has the dropped records listed as well.
@@ -20,6 +20,7 @@
 #include "../../include/circkit.h"
 #include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
 #include "ck_compact_launch.h"
+#include "ck_scan.h"
 #include "monomerize.h"
 #include "monomer_compact.h"
 
@@ -64,34 +65,16 @@ __global__ __launch_bounds__(COMPACT_WG) void compact_decide_kernel(const uint64
 
 struct Pair { uint64_t cnt, bytes; };                 // written records, written bytes
 __device__ inline Pair pair_of(uint64_t w) { return Pair{ w >> 63, w & ~ck_compact::WRITTEN }; }
-
-// inclusive scan over the workgroup; *total = the workgroup's sum
-__device__ inline Pair block_scan(Pair v, Pair* lds, Pair* total)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < CSCAN_WG; d <<= 1) {
-        Pair add{ 0, 0 };
-        if (threadIdx.x >= (unsigned)d) add = lds[threadIdx.x - d];
-        __syncthreads();
-        lds[threadIdx.x].cnt += add.cnt;
-        lds[threadIdx.x].bytes += add.bytes;
-        __syncthreads();
-    }
-    const Pair r = lds[threadIdx.x];
-    *total = lds[CSCAN_WG - 1];
-    __syncthreads();
-    return r;
-}
+struct PairAdd {                                      // the scan's operation (ck_scan.h): both sums at once
+    typedef Pair T;
+    CK_DEV T identity() { return Pair{ 0, 0 }; }
+    CK_DEV T combine(T earlier, T later) { return Pair{ earlier.cnt + later.cnt, earlier.bytes + later.bytes }; }
+};
 
 __global__ __launch_bounds__(CSCAN_WG) void compact_tile_sums_kernel(const uint64_t* __restrict__ w, uint64_t n, Pair* __restrict__ sums)
 {
     __shared__ Pair lds[CSCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * CSCAN_TILE + (uint64_t)threadIdx.x * CSCAN_ITEMS;
-    Pair v{ 0, 0 }, total;
-    for (int k = 0; k < CSCAN_ITEMS; ++k)
-        if (t0 + k < n) { const Pair x = pair_of(w[t0 + k]); v.cnt += x.cnt; v.bytes += x.bytes; }
-    block_scan(v, lds, &total);
+    const Pair total = ck_scan::tile_sum<CSCAN_WG, CSCAN_ITEMS, PairAdd>(threadIdx.x, blockIdx.x, w, n, [](uint64_t x) { return pair_of(x); }, lds);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -102,16 +85,7 @@ __global__ __launch_bounds__(CSCAN_WG) void compact_scan_sums_kernel(Pair* __res
                                                                      uint64_t* __restrict__ out_offsets, uint64_t* __restrict__ totals)
 {
     __shared__ Pair lds[CSCAN_WG];
-    Pair carry{ 0, 0 };
-    for (uint64_t b = 0; b < n_tiles; b += CSCAN_WG) {
-        const uint64_t idx = b + threadIdx.x;
-        Pair v{ 0, 0 }, chunk;
-        if (idx < n_tiles) v = sums[idx];
-        const Pair inc = block_scan(v, lds, &chunk);
-        if (idx < n_tiles) sums[idx] = Pair{ carry.cnt + inc.cnt - v.cnt, carry.bytes + inc.bytes - v.bytes };
-        carry.cnt += chunk.cnt;
-        carry.bytes += chunk.bytes;
-    }
+    const Pair carry = ck_scan::sums_exclusive<CSCAN_WG, PairAdd>(threadIdx.x, sums, n_tiles, lds);
     if (threadIdx.x == 0) {
         bool overlap = false;
         if (n) {
@@ -139,15 +113,8 @@ __global__ __launch_bounds__(CSCAN_WG) void compact_apply_kernel(const uint64_t*
     if (totals[T_OVERLAP]) return;                    // the same for the whole grid
     const uint64_t t0 = (uint64_t)blockIdx.x * CSCAN_TILE + (uint64_t)threadIdx.x * CSCAN_ITEMS;
     uint64_t loc[CSCAN_ITEMS];
-    Pair v{ 0, 0 }, total;
-    for (int k = 0; k < CSCAN_ITEMS; ++k) {
-        loc[k] = t0 + k < n ? w[t0 + k] : 0;
-        const Pair x = pair_of(loc[k]);
-        v.cnt += x.cnt; v.bytes += x.bytes;
-    }
-    const Pair inc = block_scan(v, lds, &total);
-    const Pair base = sums[blockIdx.x];
-    uint64_t j = base.cnt + inc.cnt - v.cnt, at = base.bytes + inc.bytes - v.bytes;
+    const Pair base = ck_scan::tile_base<CSCAN_WG, CSCAN_ITEMS, PairAdd>(threadIdx.x, blockIdx.x, w, n, [](uint64_t x) { return pair_of(x); }, sums, lds, loc);
+    uint64_t j = base.cnt, at = base.bytes;
     for (int k = 0; k < CSCAN_ITEMS; ++k) {
         if (!(loc[k] & ck_compact::WRITTEN)) {
             if (t0 + k < n) {
@@ -190,7 +157,7 @@ struct MonoState {                   // host-buffer form staging (grow only)
     uint64_t* d_w = nullptr; uint64_t cap_w = 0;
     Pair* d_sums = nullptr; uint64_t cap_sums = 0;
     uint64_t* d_src_start = nullptr; uint64_t cap_src_start = 0;
-    ck_compact_totals totals;
+    ck_totals totals;                // [T_WORDS], made at the first compact
     bool host_last = false;          // the last compact was the host form: its totals are host_totals
     uint64_t host_totals[T_WORDS] = { 0, 0, 0 };
     // compact, host-buffer form staging
@@ -207,7 +174,7 @@ void release_state(void* p)
     if (!S) return;
     void* ptrs[] = { S->d_in, S->d_off, S->d_end, S->d_w, S->d_sums, S->d_src_start, S->d_out, S->d_out_off, S->d_out_src, S->d_kept, S->d_full };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_compact_totals_release(&S->totals);
+    ck_totals_release(&S->totals);
     delete S;
 }
 
@@ -216,16 +183,6 @@ MonoState* state(circkit_ctx* c)
     void** slot = ck_ctx_slot(c, CK_UNIT_MONOMERIZE, release_state);
     if (!*slot) *slot = new MonoState();
     return (MonoState*)*slot;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
 }
 
 // MonomerizerBuilder::validate (lib/src/monomerize.rs:20-40) + the CLI's range check of the identity (src/monomerize.rs:40-44)
@@ -287,32 +244,25 @@ int check_totals(circkit_ctx* c, const uint64_t* t)
 }  // namespace
 
 // ---- ck_compact_launch.h: the scan, apply and gather for whoever filled w ----------------------------------------------------
-void ck_compact_totals_release(ck_compact_totals* T)
-{
-    if (T->d) (void)hipFree(T->d);
-    if (T->h) (void)hipHostFree(T->h);
-    T->d = T->h = nullptr;
-}
-
 int ck_compact_reserve(circkit_ctx* c, uint64_t n, uint64_t** d_w)
 {
     MonoState* S = state(c);
     const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
     int rc;
-    if ((rc = grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
-    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
-    if ((rc = grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
     *d_w = S->d_w;
     return CIRCKIT_OK;
 }
 
-int ck_compact_launch(circkit_ctx* c, ck_compact_totals* T, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
+int ck_compact_launch(circkit_ctx* c, ck_totals* T, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                       uint8_t* d_out_bytes, uint64_t* d_out_offsets, uint64_t* d_out_src, uint64_t* d_dup_src, uint64_t* d_dup_first,
                       const uint64_t* d_dup_val)
 {
     MonoState* S = state(c);                          // (sized by ck_compact_reserve for this n)
-    if (!T->d) CK_HIP(c, hipMalloc((void**)&T->d, T_WORDS * sizeof(uint64_t)));
-    if (!T->h) CK_HIP(c, hipHostMalloc((void**)&T->h, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    int rc;
+    if ((rc = ck_totals_make(c, T, T_WORDS))) return rc;
     const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
     hipStream_t st = ck_ctx_stream(c);
     if (n) hipLaunchKernelGGL(compact_tile_sums_kernel, dim3((uint32_t)tiles), dim3(CSCAN_WG), 0, st, (const uint64_t*)S->d_w, n, S->d_sums);
@@ -325,8 +275,7 @@ int ck_compact_launch(circkit_ctx* c, ck_compact_totals* T, const uint8_t* d_byt
                            (const uint64_t*)d_out_offsets, (const uint64_t*)S->d_src_start, (const uint64_t*)T->d, d_out_bytes);
     }
     CK_HIP(c, hipGetLastError());
-    CK_HIP(c, hipMemcpyAsync(T->h, T->d, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    return CIRCKIT_OK;
+    return ck_totals_fetch(c, T, T_WORDS);
 }
 
 extern "C" {
@@ -362,9 +311,9 @@ int circkit_monomerize_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     MonoState* S = state(c);
     const uint64_t nb = offsets[n];
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if ((rc = grow(c, &S->d_end, &S->cap_end, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_end, &S->cap_end, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -438,14 +387,14 @@ int circkit_monomers_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     S->host_totals[T_RECORDS] = S->host_totals[T_BYTES] = S->host_totals[T_OVERLAP] = 0;
     if (n == 0) return CIRCKIT_OK;
     const uint64_t nb = offsets[n];
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if ((rc = grow(c, &S->d_end, &S->cap_end, n))) return rc;
-    if ((rc = grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
-    if ((rc = grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
-    if ((rc = grow(c, &S->d_kept, &S->cap_kept, n))) return rc;
-    if (full_len && (rc = grow(c, &S->d_full, &S->cap_full, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_end, &S->cap_end, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_kept, &S->cap_kept, n))) return rc;
+    if (full_len && (rc = ck_grow(c, &S->d_full, &S->cap_full, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));

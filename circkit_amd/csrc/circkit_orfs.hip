@@ -15,6 +15,7 @@
 
 #include "../../include/circkit.h"
 #include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
+#include "ck_scan.h"
 #include "orfs.h"
 
 using ck_orfs::Orf;
@@ -26,7 +27,7 @@ static_assert(sizeof(Orf) == sizeof(circkit_orf), "device ORF layout");
 namespace {
 
 constexpr int ORF_WG = 256;
-constexpr int SCAN_WG = 1024, SCAN_ITEMS = 8, SCAN_TILE = SCAN_WG * SCAN_ITEMS;
+constexpr int SCAN_WG = 1024, SCAN_ITEMS = 8, SCAN_TILE = SCAN_WG * SCAN_ITEMS;      // the scan of the counts (ck_scan.h)
 
 struct OrfArgs {
     uint8_t cls[512];        // codon class table: bit 0 start set, bit 1 stop set
@@ -84,59 +85,25 @@ __global__ __launch_bounds__(ORF_WG) void orfs_emit_kernel(const uint8_t* __rest
     ck_orfs::sort_run(orfs + base + nf, (uint32_t)(end - base) - nf, A.F.mode);
 }
 
-// ---- exclusive scan of uint64 counts, in place: a[0..n) (a[-1] is the 0 the count kernel wrote) ----
-__device__ inline uint64_t block_inclusive_scan(uint64_t v, uint64_t* lds)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < SCAN_WG; d <<= 1) {
-        const uint64_t add = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const uint64_t r = lds[threadIdx.x];
-    __syncthreads();
-    return r;
-}
-
+// ---- exclusive scan of uint64 counts, in place: a[0..n) (a[-1] is the 0 the count kernel wrote); the bodies are ck_scan.h's ----
 __global__ __launch_bounds__(SCAN_WG) void scan_tile_sums(const uint64_t* __restrict__ a, uint64_t n, uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k) if (t0 + k < n) v += a[t0 + k];
-    v = block_inclusive_scan(v, lds);
-    if (threadIdx.x == SCAN_WG - 1) sums[blockIdx.x] = v;
+    const uint64_t total = ck_scan::tile_sum<SCAN_WG, SCAN_ITEMS, ck_scan::Add>(threadIdx.x, blockIdx.x, a, n, [](uint64_t w) { return w; }, lds);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(SCAN_WG) void scan_sums(uint64_t* __restrict__ sums, uint64_t n_tiles)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < n_tiles; b += SCAN_WG) {
-        const uint64_t idx = b + threadIdx.x;
-        const uint64_t v = idx < n_tiles ? sums[idx] : 0;
-        const uint64_t inc = block_inclusive_scan(v, lds);
-        const uint64_t chunk = lds[SCAN_WG - 1];
-        if (idx < n_tiles) sums[idx] = carry + inc - v;      // exclusive
-        carry += chunk;
-        __syncthreads();
-    }
+    ck_scan::sums_exclusive<SCAN_WG, ck_scan::Add>(threadIdx.x, sums, n_tiles, lds);
 }
 
+// inclusive over counts = exclusive over records (a = offsets + 1)
 __global__ __launch_bounds__(SCAN_WG) void scan_apply(uint64_t* __restrict__ a, uint64_t n, const uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[SCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t loc[SCAN_ITEMS];
-    uint64_t v = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k) { loc[k] = t0 + k < n ? a[t0 + k] : 0; v += loc[k]; }
-    uint64_t run = block_inclusive_scan(v, lds) - v + sums[blockIdx.x];
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        run += loc[k];
-        if (t0 + k < n) a[t0 + k] = run;                     // inclusive over counts = exclusive over records (a = offsets + 1)
-    }
+    ck_scan::apply_ends<SCAN_WG, SCAN_ITEMS, ck_scan::Add>(threadIdx.x, blockIdx.x, a, n, sums, lds);
 }
 
 struct OrfState {
@@ -167,16 +134,6 @@ OrfState* state(circkit_ctx* c)
     void** slot = ck_ctx_slot(c, CK_UNIT_ORFS, release_state);
     if (!*slot) *slot = new OrfState();
     return (OrfState*)*slot;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
 }
 
 int make_args(circkit_ctx* c, const circkit_orf_params* p, OrfArgs* A)
@@ -215,7 +172,7 @@ int launch_count(circkit_ctx* c, OrfState* S, const uint8_t* d_bytes, const uint
     CK_HIP(c, hipGetLastError());
     if (n == 0) return CIRCKIT_OK;
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    int rc = grow(c, &S->d_sums, &S->cap_sums, tiles);
+    int rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles);
     if (rc) return rc;
     hipLaunchKernelGGL(scan_tile_sums, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_orf_offsets + 1, n, S->d_sums);
     hipLaunchKernelGGL(scan_sums, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles);
@@ -288,9 +245,9 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     OrfState* S = state(c);
     const uint64_t nb = offsets[n];
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_rec, n + 1))) return rc;
-    if ((rc = grow(c, &S->d_orf_off, &S->cap_orf_off, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_rec, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_orf_off, &S->cap_orf_off, n + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -306,7 +263,7 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         return ck_ctx_fail(c, CIRCKIT_ERR_OOM, m);
     }
     if (t == 0) return CIRCKIT_OK;
-    if ((rc = grow(c, &S->d_orfs, &S->cap_orfs, t))) return rc;
+    if ((rc = ck_grow(c, &S->d_orfs, &S->cap_orfs, t))) return rc;
     if ((rc = launch_emit(c, S->d_in, S->d_off, n, A, S->d_orf_off, S->d_orfs, t))) return rc;
     CK_HIP(c, hipMemcpyAsync(orfs, S->d_orfs, t * sizeof(Orf), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));

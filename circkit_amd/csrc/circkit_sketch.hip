@@ -49,10 +49,8 @@ __global__ __launch_bounds__(64 * COMPARE_WAVES) void sketch_compare_kernel(Comp
 }
 
 struct SketchState {
-    uint64_t* d_totals = nullptr;    // [T_WORDS]
-    uint64_t* h_totals = nullptr;    // the same, page-locked: valid once the ctx stream has run past the copy
-    uint64_t* d_invalid = nullptr;   // the invalid pairs of the most recent compare
-    uint64_t* h_invalid = nullptr;
+    ck_totals totals;                // [T_WORDS], of the most recent sketch; both made with the state
+    ck_totals invalid;               // [1]: the invalid pairs of the most recent compare
     bool any = false, any_compare = false;
     uint64_t* d_long = nullptr; uint64_t cap_long = 0;          // the list of long records (grow only, n_records entries)
     // the staging of the host forms (grow only)
@@ -69,10 +67,10 @@ void release_state(void* p)
 {
     SketchState* S = (SketchState*)p;
     if (!S) return;
-    void* ptrs[] = { S->d_totals, S->d_invalid, S->d_long, S->d_bytes, S->d_off, S->d_rows, S->d_counts, S->d_rows_b, S->d_pairs, S->d_result };
+    void* ptrs[] = { S->d_long, S->d_bytes, S->d_off, S->d_rows, S->d_counts, S->d_rows_b, S->d_pairs, S->d_result };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_totals) (void)hipHostFree(S->h_totals);
-    if (S->h_invalid) (void)hipHostFree(S->h_invalid);
+    ck_totals_release(&S->totals);
+    ck_totals_release(&S->invalid);
     delete S;
 }
 
@@ -82,27 +80,9 @@ int state(circkit_ctx* c, SketchState** out)
     if (!*slot) *slot = new SketchState();
     SketchState* S = (SketchState*)*slot;
     *out = S;
-    if (!S->d_totals) CK_HIP(c, hipMalloc((void**)&S->d_totals, T_WORDS * sizeof(uint64_t)));
-    if (!S->d_invalid) CK_HIP(c, hipMalloc((void**)&S->d_invalid, sizeof(uint64_t)));
-    if (!S->h_totals) {
-        CK_HIP(c, hipHostMalloc((void**)&S->h_totals, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
-        for (int k = 0; k < T_WORDS; ++k) S->h_totals[k] = 0;
-    }
-    if (!S->h_invalid) {
-        CK_HIP(c, hipHostMalloc((void**)&S->h_invalid, sizeof(uint64_t), hipHostMallocDefault));
-        *S->h_invalid = 0;
-    }
-    return CIRCKIT_OK;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
+    int rc;
+    if ((rc = ck_totals_make(c, &S->totals, T_WORDS))) return rc;
+    return ck_totals_make(c, &S->invalid, 1);
 }
 
 bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
@@ -126,22 +106,22 @@ int launch_sketch(circkit_ctx* c, SketchState* S, const uint8_t* d_bytes, const 
                   uint64_t* d_out, uint32_t* d_counts)
 {
     int rc;
-    if ((rc = grow(c, &S->d_long, &S->cap_long, n ? n : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_long, &S->cap_long, n ? n : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(S->d_totals, 0, T_WORDS * sizeof(uint64_t), st));
+    if ((rc = ck_totals_clear(c, &S->totals, T_WORDS))) return rc;
     if (n) {
         Sketch K;
         K.bytes = d_bytes; K.offsets = d_offsets; K.n_records = n;
         K.k = p.k; K.log2_bins = p.log2_bins; K.seed = p.seed;
         K.out = d_out; K.out_count = d_counts;
-        K.long_list = S->d_long; K.totals = S->d_totals;
+        K.long_list = S->d_long; K.totals = S->totals.d;
         const uint64_t blocks = (n + SKETCH_WAVES - 1) / SKETCH_WAVES;
         const size_t lds = (size_t)SKETCH_WAVES * ck_sketch::lds_words(p.log2_bins) * sizeof(uint64_t);
         hipLaunchKernelGGL(sketch_short_kernel, dim3((uint32_t)(blocks > SHORT_MAX_GRID ? SHORT_MAX_GRID : blocks)), dim3(64 * SKETCH_WAVES), lds, st, K);
         hipLaunchKernelGGL(sketch_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), lds, st, K);
         CK_HIP(c, hipGetLastError());
     }
-    CK_HIP(c, hipMemcpyAsync(S->h_totals, S->d_totals, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
     S->any = true;
     return CIRCKIT_OK;
 }
@@ -158,18 +138,19 @@ int launch_compare(circkit_ctx* c, SketchState* S, const uint64_t* d_a, uint64_t
                    const uint32_t* d_pairs, uint64_t n_pairs, uint32_t* d_out)
 {
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(S->d_invalid, 0, sizeof(uint64_t), st));
+    int rc;
+    if ((rc = ck_totals_clear(c, &S->invalid, 1))) return rc;
     if (n_pairs) {
         Compare C;
         C.a = d_a; C.b = d_b; C.n_a = n_a; C.n_b = n_b;
         C.log2_bins = log2_bins;
         C.pairs = d_pairs; C.n_pairs = n_pairs;
-        C.out = d_out; C.n_invalid = S->d_invalid;
+        C.out = d_out; C.n_invalid = S->invalid.d;
         const uint64_t blocks = (n_pairs + COMPARE_WAVES - 1) / COMPARE_WAVES;
         hipLaunchKernelGGL(sketch_compare_kernel, dim3((uint32_t)(blocks > COMPARE_MAX_GRID ? COMPARE_MAX_GRID : blocks)), dim3(64 * COMPARE_WAVES), 0, st, C);
         CK_HIP(c, hipGetLastError());
     }
-    CK_HIP(c, hipMemcpyAsync(S->h_invalid, S->d_invalid, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = ck_totals_fetch(c, &S->invalid, 1))) return rc;
     S->any_compare = true;
     return CIRCKIT_OK;
 }
@@ -223,7 +204,7 @@ int circkit_sketch_status(circkit_ctx* c, uint64_t* n_valid_kmers_total, uint32_
     if ((rc = state(c, &S))) return rc;
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t none[T_WORDS] = { 0, 0, 0 };
-    const uint64_t* t = S->any ? S->h_totals : none;
+    const uint64_t* t = S->any ? S->totals.h : none;
     if (n_valid_kmers_total) *n_valid_kmers_total = t[ck_sketch::T_VALID];
     if (n_unprocessed) *n_unprocessed = t[ck_sketch::T_UNPROCESSED] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t[ck_sketch::T_UNPROCESSED];
     return check_totals(c, t);
@@ -254,7 +235,7 @@ int circkit_sketch_compare_status(circkit_ctx* c, uint64_t* n_invalid)
     int rc;
     if ((rc = state(c, &S))) return rc;
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
-    const uint64_t bad = S->any_compare ? *S->h_invalid : 0;
+    const uint64_t bad = S->any_compare ? S->invalid.h[0] : 0;
     if (n_invalid) *n_invalid = bad;
     return check_invalid(c, bad);
 }
@@ -280,10 +261,10 @@ int circkit_sketch_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* o
     SketchState* S;
     if ((rc = state(c, &S))) return rc;
     const uint64_t n_rows = n_records << params->log2_bins;
-    if ((rc = grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
-    if ((rc = grow(c, &S->d_counts, &S->cap_counts, n_records ? n_records : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_counts, &S->cap_counts, n_records ? n_records : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
     if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -291,7 +272,7 @@ int circkit_sketch_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* o
     if (n_rows) CK_HIP(c, hipMemcpyAsync(out_sketch, S->d_rows, n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (n_records && out_n_kmers) CK_HIP(c, hipMemcpyAsync(out_n_kmers, S->d_counts, n_records * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
-    return check_totals(c, S->h_totals);
+    return check_totals(c, S->totals.h);
 }
 
 int circkit_sketch_compare(circkit_ctx* c, const uint64_t* sketch_a, uint64_t n_a, const uint64_t* sketch_b, uint64_t n_b, uint32_t log2_bins,
@@ -306,10 +287,10 @@ int circkit_sketch_compare(circkit_ctx* c, const uint64_t* sketch_a, uint64_t n_
     if ((rc = state(c, &S))) return rc;
     const bool same = sketch_a == sketch_b;
     const uint64_t wa = (same && n_b > n_a ? n_b : n_a) << log2_bins, wb = same ? 0 : n_b << log2_bins;
-    if ((rc = grow(c, &S->d_rows, &S->cap_rows, wa ? wa : 1))) return rc;
-    if ((rc = grow(c, &S->d_rows_b, &S->cap_rows_b, wb ? wb : 1))) return rc;
-    if ((rc = grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if ((rc = grow(c, &S->d_result, &S->cap_result, n_pairs ? 2 * n_pairs : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, wa ? wa : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_rows_b, &S->cap_rows_b, wb ? wb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_result, &S->cap_result, n_pairs ? 2 * n_pairs : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (n_pairs && wa) CK_HIP(c, hipMemcpyAsync(S->d_rows, sketch_a, wa * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (n_pairs && wb) CK_HIP(c, hipMemcpyAsync(S->d_rows_b, sketch_b, wb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -317,7 +298,7 @@ int circkit_sketch_compare(circkit_ctx* c, const uint64_t* sketch_a, uint64_t n_
     if ((rc = launch_compare(c, S, S->d_rows, n_a, same ? S->d_rows : S->d_rows_b, n_b, log2_bins, S->d_pairs, n_pairs, S->d_result))) return rc;
     if (n_pairs) CK_HIP(c, hipMemcpyAsync(out, S->d_result, 2 * n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
-    return check_invalid(c, *S->h_invalid);
+    return check_invalid(c, S->invalid.h[0]);
 }
 
 }  // extern "C"

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(DECIDE_WG) void uniq_compact_decide_kernel(const ui
 }
 
 struct UniqCompactState {
-    ck_compact_totals totals;            // of the most recent uniq compact of this ctx
+    ck_totals totals;                    // [CK_COMPACT_WORDS], of the most recent uniq compact of this ctx
     // circkit_uniq_batch's staging (grow only)
     uint8_t* d_in = nullptr; uint64_t cap_in = 0;
     uint64_t* d_off = nullptr; uint64_t cap_off = 0;
@@ -49,7 +49,7 @@ void release_state(void* p)
     if (!S) return;
     void* ptrs[] = { S->d_in, S->d_off, S->d_canon, S->d_hash, S->d_fs, S->d_out, S->d_out_off, S->d_out_src };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_compact_totals_release(&S->totals);
+    ck_totals_release(&S->totals);
     delete S;
 }
 
@@ -58,16 +58,6 @@ UniqCompactState* state(circkit_ctx* c)
     void** slot = ck_ctx_slot(c, CK_UNIT_UNIQ_COMPACT, release_state);
     if (!*slot) *slot = new UniqCompactState();
     return (UniqCompactState*)*slot;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
 }
 
 // the decide kernel and the shared kernels behind it, on the ctx stream; nothing waits
@@ -141,14 +131,14 @@ int circkit_uniq_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         return CIRCKIT_OK;
     }
     const uint64_t nb = offsets[n];
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if (canonical_out && (rc = grow(c, &S->d_canon, &S->cap_canon, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_hash, &S->cap_hash, n))) return rc;
-    if ((rc = grow(c, &S->d_fs, &S->cap_fs, n))) return rc;
-    if ((rc = grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
-    if ((rc = grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
+    if (canonical_out && (rc = ck_grow(c, &S->d_canon, &S->cap_canon, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_hash, &S->cap_hash, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_fs, &S->cap_fs, n))) return rc;
+    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));

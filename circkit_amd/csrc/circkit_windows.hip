@@ -8,8 +8,9 @@
 //                              capacity and the refusal of an output that overlaps the payload
 //   windows_apply_kernel       out_offsets in place: the lengths become the offsets
 //   windows_gather_kernel      window_gather.h gather_tile over the output tiles, unless the scan refused the gather
-// The sums saturate (window_gather.h sat_add), so out_offsets never decreases whatever lengths the windows name.  The totals
-// stay in device memory and are copied to pinned memory behind the gather: circkit_windows_status waits and reads them.
+// The three scan kernels are ck_scan.h's bodies with WSCAN_WG, WSCAN_ITEMS and the saturating sum (ck_scan::SatAdd), so
+// out_offsets never decreases whatever lengths the windows name.  The totals stay in device memory and are
+// copied to pinned memory behind the gather: circkit_windows_status waits and reads them.
 // A translate (window_translate.h) is the same five steps with its own first and last: windows_residues_kernel counts residues
 // (a third of the bytes, rounded down), the three scan kernels run as they are, windows_translate_kernel runs translate_tile
 // over the output tiles.  Its totals are its own, so circkit_windows_status and circkit_translate_status each answer for the
@@ -22,6 +23,7 @@
 
 #include "../../include/circkit.h"
 #include "ck_ctx.h"
+#include "ck_scan.h"
 #include "window_gather.h"
 #include "window_translate.h"
 
@@ -66,30 +68,10 @@ __global__ __launch_bounds__(WIN_WG) void windows_residues_kernel(const uint64_t
     }
 }
 
-// exclusive scan over the workgroup, saturating; *total = the workgroup's sum
-__device__ inline uint64_t block_scan(uint64_t v, uint64_t* lds, uint64_t* total)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < WSCAN_WG; d <<= 1) {
-        const uint64_t add = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] = ck_windows::sat_add(lds[threadIdx.x], add);
-        __syncthreads();
-    }
-    const uint64_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0;
-    *total = lds[WSCAN_WG - 1];
-    __syncthreads();
-    return before;
-}
-
 __global__ __launch_bounds__(WSCAN_WG) void windows_tile_sums_kernel(const uint64_t* __restrict__ len, uint64_t m, uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[WSCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * WSCAN_TILE + (uint64_t)threadIdx.x * WSCAN_ITEMS;
-    uint64_t v = 0, total;
-    for (int k = 0; k < WSCAN_ITEMS; ++k) if (t0 + k < m) v = ck_windows::sat_add(v, len[t0 + k]);
-    block_scan(v, lds, &total);
+    const uint64_t total = ck_scan::tile_sum<WSCAN_WG, WSCAN_ITEMS, ck_scan::SatAdd>(threadIdx.x, blockIdx.x, len, m, [](uint64_t w) { return w; }, lds);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -101,16 +83,8 @@ __global__ __launch_bounds__(WSCAN_WG) void windows_scan_sums_kernel(uint64_t* _
                                                                      uint64_t* __restrict__ totals)
 {
     __shared__ uint64_t lds[WSCAN_WG];
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < n_tiles; b += WSCAN_WG) {
-        const uint64_t idx = b + threadIdx.x;
-        uint64_t chunk;
-        const uint64_t before = block_scan(idx < n_tiles ? sums[idx] : 0, lds, &chunk);
-        if (idx < n_tiles) sums[idx] = ck_windows::sat_add(carry, before);
-        carry = ck_windows::sat_add(carry, chunk);
-    }
+    const uint64_t total = ck_scan::sums_exclusive<WSCAN_WG, ck_scan::SatAdd>(threadIdx.x, sums, n_tiles, lds);
     if (threadIdx.x == 0) {
-        const uint64_t total = carry;
         uint64_t refused = total > capacity || total == ~0ull ? REFUSED_CAPACITY : 0;
         if (!refused && total && out && n_records) {
             const uint64_t p0 = offsets[0], p1 = offsets[n_records];
@@ -127,15 +101,7 @@ __global__ __launch_bounds__(WSCAN_WG) void windows_scan_sums_kernel(uint64_t* _
 __global__ __launch_bounds__(WSCAN_WG) void windows_apply_kernel(uint64_t* __restrict__ ends, uint64_t m, const uint64_t* __restrict__ sums)
 {
     __shared__ uint64_t lds[WSCAN_WG];
-    const uint64_t t0 = (uint64_t)blockIdx.x * WSCAN_TILE + (uint64_t)threadIdx.x * WSCAN_ITEMS;
-    uint64_t loc[WSCAN_ITEMS];
-    uint64_t v = 0, total;
-    for (int k = 0; k < WSCAN_ITEMS; ++k) { loc[k] = t0 + k < m ? ends[t0 + k] : 0; v = ck_windows::sat_add(v, loc[k]); }
-    uint64_t run = ck_windows::sat_add(sums[blockIdx.x], block_scan(v, lds, &total));
-    for (int k = 0; k < WSCAN_ITEMS; ++k) {
-        run = ck_windows::sat_add(run, loc[k]);
-        if (t0 + k < m) ends[t0 + k] = run;
-    }
+    ck_scan::apply_ends<WSCAN_WG, WSCAN_ITEMS, ck_scan::SatAdd>(threadIdx.x, blockIdx.x, ends, m, sums, lds);
 }
 
 __global__ __launch_bounds__(64 * ck_windows::GATHER_WAVES) void windows_gather_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets,
@@ -219,9 +185,7 @@ __global__ __launch_bounds__(WIN_WG) void orfs_windows_kernel(const uint64_t* __
 }
 
 // the totals of the most recent gather, or of the most recent translate: each kind of call has its own
-struct Totals {
-    uint64_t* d = nullptr;           // [T_WORDS], device
-    uint64_t* h = nullptr;           // the same, page-locked host memory: valid once the ctx stream has run past the copy
+struct Totals : ck_totals {          // [T_WORDS], made at the first call of the kind
     uint64_t capacity = 0;           // of that call, for the status message
     bool any = false;
 };
@@ -241,10 +205,10 @@ void release_state(void* p)
 {
     WindowsState* S = (WindowsState*)p;
     if (!S) return;
-    void* ptrs[] = { S->gather.d, S->translate.d, S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
+    void* ptrs[] = { S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
     for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->gather.h) (void)hipHostFree(S->gather.h);
-    if (S->translate.h) (void)hipHostFree(S->translate.h);
+    ck_totals_release(&S->gather);
+    ck_totals_release(&S->translate);
     delete S;
 }
 
@@ -253,16 +217,6 @@ WindowsState* state(circkit_ctx* c)
     void** slot = ck_ctx_slot(c, CK_UNIT_WINDOWS, release_state);
     if (!*slot) *slot = new WindowsState();
     return (WindowsState*)*slot;
-}
-
-template <typename T>
-int grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
-{
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
 }
 
 uint32_t lane_grid(uint64_t items)
@@ -276,13 +230,12 @@ uint32_t lane_grid(uint64_t items)
 int launch_offsets(circkit_ctx* c, WindowsState* S, Totals* R, bool residues, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
                    const Window* d_windows, uint64_t m, const uint8_t* d_out, uint64_t capacity, uint64_t* d_out_offsets)
 {
-    if (!R->d) CK_HIP(c, hipMalloc((void**)&R->d, T_WORDS * sizeof(uint64_t)));
-    if (!R->h) CK_HIP(c, hipHostMalloc((void**)&R->h, T_WORDS * sizeof(uint64_t), hipHostMallocDefault));
-    const uint64_t tiles = (m + WSCAN_TILE - 1) / WSCAN_TILE;
     int rc;
-    if ((rc = grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = ck_totals_make(c, R, T_WORDS))) return rc;
+    const uint64_t tiles = (m + WSCAN_TILE - 1) / WSCAN_TILE;
+    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    CK_HIP(c, hipMemsetAsync(R->d, 0, T_WORDS * sizeof(uint64_t), st));
+    if ((rc = ck_totals_clear(c, R, T_WORDS))) return rc;
     if (m) {
         if (residues)
             hipLaunchKernelGGL(windows_residues_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
@@ -316,12 +269,6 @@ int launch_translate(circkit_ctx* c, WindowsState* S, const uint8_t* d_bytes, co
     hipLaunchKernelGGL(windows_translate_kernel, dim3(GATHER_GRID), dim3(64 * ck_translate::TRANSLATE_WAVES), 0, ck_ctx_stream(c), d_bytes, d_offsets,
                        n_records, d_windows, m, d_out_offsets, (const uint64_t*)S->translate.d, ck_ctx_complement(c), params, d_out);
     CK_HIP(c, hipGetLastError());
-    return CIRCKIT_OK;
-}
-
-int copy_totals(circkit_ctx* c, Totals* R)
-{
-    CK_HIP(c, hipMemcpyAsync(R->h, R->d, T_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
     return CIRCKIT_OK;
 }
 
@@ -374,7 +321,7 @@ int circkit_windows_gather_device(circkit_ctx* c, const uint8_t* d_bytes, const 
                              d_out_offsets)))
         return rc;
     if ((rc = launch_gather(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, d_out_offsets, d_out_bytes))) return rc;
-    return copy_totals(c, &S->gather);
+    return ck_totals_fetch(c, &S->gather, T_WORDS);
 }
 
 int circkit_windows_status(circkit_ctx* c, uint64_t* total_bytes, uint64_t* n_invalid)
@@ -435,17 +382,17 @@ int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     WindowsState* S = state(c);
     int rc;
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
-    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
     // the offsets first: the staging for the bytes is sized by the total they end in (it cannot overlap the staged payload)
     if ((rc = launch_offsets(c, S, &S->gather, false, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = copy_totals(c, &S->gather))) return rc;
+    if ((rc = ck_totals_fetch(c, &S->gather, T_WORDS))) return rc;
     CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
     const uint64_t B = S->gather.h[T_TOTAL];
@@ -453,7 +400,7 @@ int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     if (S->gather.h[T_REFUSED]) return check_totals(c, S->gather.h, out_capacity);
     if (B) {
         if (!out_bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
         if ((rc = launch_gather(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, S->d_out_off, S->d_out))) return rc;
         CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
         CK_HIP(c, hipStreamSynchronize(st));
@@ -477,7 +424,7 @@ int circkit_windows_translate_device(circkit_ctx* c, const uint8_t* d_bytes, con
                              d_out_offsets)))
         return rc;
     if ((rc = launch_translate(c, S, d_bytes, d_offsets, n_records, (const Window*)d_windows, n_windows, *params, d_out_offsets, d_out_aa))) return rc;
-    return copy_totals(c, &S->translate);
+    return ck_totals_fetch(c, &S->translate, T_WORDS);
 }
 
 int circkit_translate_status(circkit_ctx* c, uint64_t* total_residues, uint64_t* n_invalid)
@@ -509,17 +456,17 @@ int circkit_windows_translate(circkit_ctx* c, const uint8_t* bytes, const uint64
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     WindowsState* S = state(c);
     Totals* R = &S->translate;
-    if ((rc = grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
-    if ((rc = grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
+    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
     if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
     // the offsets first: the staging for the residues is sized by the total they end in (it cannot overlap the staged payload)
     if ((rc = launch_offsets(c, S, R, true, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = copy_totals(c, R))) return rc;
+    if ((rc = ck_totals_fetch(c, R, T_WORDS))) return rc;
     CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     CK_HIP(c, hipStreamSynchronize(st));
     const uint64_t B = R->h[T_TOTAL];
@@ -527,7 +474,7 @@ int circkit_windows_translate(circkit_ctx* c, const uint8_t* bytes, const uint64
     if (R->h[T_REFUSED]) return check_translate_totals(c, R->h, out_capacity);
     if (B) {
         if (!out_aa) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
         if ((rc = launch_translate(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, *params, S->d_out_off, S->d_out))) return rc;
         CK_HIP(c, hipMemcpyAsync(out_aa, S->d_out, B, hipMemcpyDeviceToHost, st));
         CK_HIP(c, hipStreamSynchronize(st));

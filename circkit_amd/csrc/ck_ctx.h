@@ -1,8 +1,9 @@
 // ck_ctx.h -- what a translation unit other than circkit_hip.hip may ask of the ctx (internal; not part of the C ABI).
 //
-// struct circkit_ctx lives in circkit_hip.hip and nothing outside that file names one of its fields.  The other units
-// (circkit_orfs.hip, circkit_monomerize.hip, circkit_uniq.hip, circkit_uniq_compact.hip, circkit_windows.hip, circkit_fasta.hip, circkit_fasta_write.hip, circkit_sketch.hip) enqueue on the ctx's stream, report through its error string
-// and keep their own state behind one slot each, which circkit_ctx_destroy releases.
+// struct circkit_ctx lives in circkit_hip.hip and nothing outside that file names one of its fields.  The other units (one
+// circkit_*.hip per ck_unit below) enqueue on the ctx's stream, report through its error string and keep their own state behind
+// one slot each, which circkit_ctx_destroy releases.  What that state is made of is here once: a grow-only device buffer
+// (ck_grow) and the totals of a unit's most recent call (ck_totals).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,3 +30,48 @@ inline int ck_ctx_fail(circkit_ctx* c, int code, const char* msg) { return ck_fa
 // finds to the `release` the unit named.
 enum ck_unit { CK_UNIT_ORFS, CK_UNIT_MONOMERIZE, CK_UNIT_UNIQ, CK_UNIT_UNIQ_COMPACT, CK_UNIT_WINDOWS, CK_UNIT_FASTA, CK_UNIT_FASTA_WRITE, CK_UNIT_SKETCH, CK_N_UNITS };
 void** ck_ctx_slot(circkit_ctx* c, ck_unit unit, void (*release)(void*));
+
+// A device buffer of a unit's state that only grows: *p holds at least `want` elements afterwards (its contents are not kept).
+template <typename T>
+int ck_grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
+{
+    if (want <= *cap) return CIRCKIT_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
+    *cap = want;
+    return CIRCKIT_OK;
+}
+
+// The totals of a unit's most recent call: a few 64-bit words that the kernels write in device memory, and the same words in
+// page-locked host memory, valid once the ctx stream has run past the copy.  How many words, and what they mean, is the unit's.
+struct ck_totals {
+    uint64_t* d = nullptr;
+    uint64_t* h = nullptr;
+};
+// both where missing; new host words are 0
+inline int ck_totals_make(circkit_ctx* c, ck_totals* T, int words)
+{
+    if (!T->d) CK_HIP(c, hipMalloc((void**)&T->d, words * sizeof(uint64_t)));
+    if (!T->h) {
+        CK_HIP(c, hipHostMalloc((void**)&T->h, words * sizeof(uint64_t), hipHostMallocDefault));
+        for (int k = 0; k < words; ++k) T->h[k] = 0;
+    }
+    return CIRCKIT_OK;
+}
+// on the ctx stream: the device words become 0 in front of the work / are copied to the host words behind it
+inline int ck_totals_clear(circkit_ctx* c, ck_totals* T, int words)
+{
+    CK_HIP(c, hipMemsetAsync(T->d, 0, words * sizeof(uint64_t), ck_ctx_stream(c)));
+    return CIRCKIT_OK;
+}
+inline int ck_totals_fetch(circkit_ctx* c, ck_totals* T, int words)
+{
+    CK_HIP(c, hipMemcpyAsync(T->h, T->d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
+    return CIRCKIT_OK;
+}
+inline void ck_totals_release(ck_totals* T)
+{
+    if (T->d) (void)hipFree(T->d);
+    if (T->h) (void)hipHostFree(T->h);
+    T->d = T->h = nullptr;
+}

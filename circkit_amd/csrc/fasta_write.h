@@ -20,6 +20,7 @@
 #pragma once
 #include <stdint.h>
 #include "wave_prims.h"
+#include "ck_scan.h"
 #include "monomer_compact.h"
 
 namespace ck_fwrite {
@@ -39,12 +40,8 @@ constexpr uint32_t TILE_BYTES = 16 * TILE_GRANULES;      // 16 KiB of output per
 constexpr uint32_t SCAN_WG = 256, SCAN_ITEMS = 2, SCAN_TILE = SCAN_WG * SCAN_ITEMS;
 enum { REFUSED_CAPACITY = 1, REFUSED_OVERLAP = 2 };
 
-// a + b, or ~0 where that does not fit (window_gather.h's rule: the scan stays monotone, and no capacity holds ~0)
-CK_DEV uint64_t sat_add(uint64_t a, uint64_t b)
-{
-    const uint64_t s = a + b;
-    return s < a ? ~0ull : s;
-}
+// a + b, or ~0 where that does not fit (the scan stays monotone, and no capacity holds ~0)
+using ck_scan::sat_add;
 
 // What the records are made of.  Exactly one of raw and body (with body_offsets) is given; src and labels may be null.
 struct Source {

@@ -21,6 +21,7 @@
 #pragma once
 #include <stdint.h>
 #include "wave_prims.h"
+#include "ck_scan.h"
 #include "monomer_compact.h"
 
 namespace ck_windows {
@@ -51,11 +52,7 @@ CK_DEV uint64_t effective_length(const Window& W, const uint64_t* offsets, uint6
 
 // a + b, or ~0 where that does not fit: the scan of the lengths stays monotone whatever lengths the windows name, and a batch
 // whose total does not fit 64 bits has the total ~0, which no capacity holds
-CK_DEV uint64_t sat_add(uint64_t a, uint64_t b)
-{
-    const uint64_t s = a + b;
-    return s < a ? ~0ull : s;
-}
+using ck_scan::sat_add;
 
 // (a + t) mod n for a < n: the one 64-bit division of a (granule, window) pair, and none where the window has not yet gone
 // round its record twice
