@@ -103,6 +103,11 @@ SIGNATURES = {
     "circkit_sketch_compare_status": (_i, [_vp, ctypes.POINTER(_u64)]),
     "circkit_sketch_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "circkit_sketch_compare": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _u64, _vp]),
+    "circkit_cluster_candidates_device": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64]),
+    "circkit_cluster_candidates_status": (_i, [_vp, ctypes.POINTER(_u64)]),
+    "circkit_cluster_link_device": (_i, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "circkit_cluster_link_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 3),
+    "circkit_cluster_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64)]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -155,6 +160,22 @@ def sketch_params(k=21, log2_bins=8, seed=0):
     xor-ed into every canonical k-mer before it is hashed.  The library checks the ranges."""
     p = SketchParams()
     p.k, p.log2_bins, p.seed = int(k), int(log2_bins), int(seed) & SKETCH_EMPTY
+    return p
+
+
+# circkit_cluster_params (include/circkit.h)
+class ClusterParams(ctypes.Structure):
+    _fields_ = [("n_bands", _u32), ("band_bins", _u32), ("min_similarity_q16", _u32), ("min_filled", _u32), ("reserved", _u32 * 2)]
+
+
+def cluster_params(n_bands=64, band_bins=2, min_similarity=0.2, min_filled=8):
+    """circkit_cluster_params from Python values: n_bands (1 .. 64) bands of band_bins (1 .. 16) bins each make the candidate
+    pairs; a scored pair links when filled >= min_filled and match / filled >= min_similarity (0 .. 1, kept as the nearest
+    multiple of 2^-16).  The library checks the ranges."""
+    p = ClusterParams()
+    q = int(round(float(min_similarity) * 65536))
+    p.n_bands, p.band_bins, p.min_filled = int(n_bands), int(band_bins), int(min_filled)
+    p.min_similarity_q16 = q if 0 <= q < 2 ** 32 else 2 ** 32 - 1
     return p
 
 
@@ -795,6 +816,50 @@ class Context:
                                                      _ptr(pairs) if m else None, m, _ptr(out) if m else None))
         return out[:, 0].copy(), out[:, 1].copy()
 
+    # -- clusters of circular records ----------------------------------------------------------------
+    def cluster_candidates_device(self, d_sketch, n_records, log2_bins, d_pair_offsets, d_pairs, capacity, params=None, **kw):
+        """Enqueues circkit_cluster_candidates_device: the candidate pairs of the sketch rows d_sketch as a CSR by the later
+        record, d_pair_offsets (uint64[n_records + 1]) and d_pairs (uint32[2 * capacity]), the layout sketch_compare_device
+        takes.  params: a cluster_params() result, or its keywords.  cluster_candidates_status() waits and returns the total."""
+        p = params if params is not None else cluster_params(**kw)
+        self._check(self._lib.circkit_cluster_candidates_device(self._h, _ptr(d_sketch), int(n_records), int(log2_bins), ctypes.byref(p),
+                                                                _ptr(d_pair_offsets), _ptr(d_pairs), int(capacity)))
+
+    def cluster_candidates_status(self):
+        """Waits for the last candidates call; returns the number of pairs.  Raises CirckitError (OOM) when they exceeded the
+        capacity: the message has the number."""
+        t = _u64(0)
+        self._check(self._lib.circkit_cluster_candidates_status(self._h, ctypes.byref(t)))
+        return t.value
+
+    def cluster_link_device(self, n_records, d_pairs, d_scores, n_pairs, d_labels, params=None, **kw):
+        """Enqueues circkit_cluster_link_device: single linkage over the pairs whose (match, filled) in d_scores pass the
+        threshold; d_labels[i] (uint64, device) = the smallest record of i's cluster.  cluster_link_status() waits."""
+        p = params if params is not None else cluster_params(**kw)
+        self._check(self._lib.circkit_cluster_link_device(self._h, int(n_records), _ptr(d_pairs), _ptr(d_scores), int(n_pairs), ctypes.byref(p),
+                                                          _ptr(d_labels)))
+
+    def cluster_link_status(self):
+        """Waits for the last link; returns (clusters, linked pairs, invalid pairs).  Raises CirckitError (INVALID_ARG) when
+        pairs were invalid."""
+        a, b, bad = _u64(0), _u64(0), _u64(0)
+        self._check(self._lib.circkit_cluster_link_status(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(bad)))
+        return a.value, b.value, bad.value
+
+    def cluster_batch(self, data, offsets, k=21, log2_bins=8, seed=0, params=None, **kw):
+        """The clusters of a host CSR batch: (labels, n_clusters); labels[i] = the smallest record of record i's cluster.  params
+        or the keywords of cluster_params."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        p = params if params is not None else cluster_params(**kw)
+        sp = sketch_params(k=k, log2_bins=log2_bins, seed=seed)
+        n = len(offsets) - 1
+        labels = np.empty(n, dtype=np.uint64)
+        m = _u64(0)
+        self._check(self._lib.circkit_cluster_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, ctypes.byref(sp), ctypes.byref(p),
+                                                    _ptr(labels) if n else None, ctypes.byref(m)))
+        return labels, m.value
+
     def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
         """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
         import torch
@@ -1128,6 +1193,16 @@ def sketch_similarity(sk_a, sk_b, pairs):
     """(match, filled) of every pair (i, j) of rows of two sketch arrays: match / filled estimates the Jaccard index of the two
     records' canonical cyclic k-mer sets."""
     return default_context().sketch_compare(sk_a, sk_b, pairs)
+
+
+def cluster_batch(seqs, k=21, log2_bins=8, seed=0, **cluster):
+    """Single-linkage clusters of a list of normalized records (bytes) over their sketches: (labels, n_clusters), labels[i] =
+    the smallest index in record i's cluster.  The keywords of cluster_params choose the bands and the threshold."""
+    seqs = [bytes(s) for s in seqs]
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    data = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    return default_context().cluster_batch(data, offsets, k=k, log2_bins=log2_bins, seed=seed, **cluster)
 
 
 def orf_proteins(data, offsets, include_stop=False, **kw):

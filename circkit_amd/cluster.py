@@ -1,0 +1,149 @@
+"""`cluster`, the first open item of the reference's roadmap, as a driver over the device calls: the driver for in-memory FASTA
+text and a thin `python -m circkit_amd.cluster` wrapper for plain FASTA files and stdin / stdout.
+
+    cluster_fasta(text, **flags) -> (fasta_bytes, table_bytes, labels)
+
+Nothing but the text goes to the device and nothing but the result comes back: the text is parsed there
+(circkit_fasta_parse_device), every record sketched (circkit_sketch_batch_device), the candidate pairs made from the bands of
+the rows (circkit_cluster_candidates_device), scored (circkit_sketch_compare_device) and linked (circkit_cluster_link_device);
+the labels are a first_seen array, so circkit_uniq_compact_device packs the representatives and lists the members, and
+circkit_fasta_write_device writes the representatives under their own heads with their normalized sequence.  The table names
+every member that is not its cluster's representative: `member<TAB>representative`, the first word of either head, under a
+title row of those two words, in input order.
+"""
+import argparse
+import sys
+
+import numpy as np
+
+from . import api
+
+
+def _word(head):
+    parts = head.split(None, 1)
+    return parts[0] if parts else b""
+
+
+def cluster_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min_similarity=0.2, min_filled=8, ctx=None):
+    """The whole chain on FASTA text: (the representatives as FASTA, the member table, the labels as a uint64 array).  Raises
+    ValueError on a FASTA format error, CirckitError on parameters out of range."""
+    import torch
+    text = bytes(text)
+    ctx = ctx or api.default_context()
+    p = api.cluster_params(n_bands=n_bands, band_bins=band_bins, min_similarity=min_similarity, min_filled=min_filled)
+    sp = api.sketch_params(k=k, log2_bins=log2_bins, seed=seed)
+    title = b"member\trepresentative\n"
+    n_text = len(text)
+    if n_text == 0:
+        return b"", title, np.zeros(0, dtype=np.uint64)
+    dev = torch.device("cuda", ctx.device)
+    cap_r = (n_text + 1) // 2
+    with torch.cuda.device(dev):
+        d_text = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(dev)
+        d_data = torch.empty(n_text, dtype=torch.uint8, device=dev)
+        d_offs = torch.empty(cap_r + 1, dtype=torch.int64, device=dev)
+        d_spans = torch.empty((2, cap_r, 2), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream().synchronize()             # the copies are torch's, the kernels the ctx stream's
+        ctx.fasta_parse_device(d_text, n_text, d_data, n_text, d_offs, cap_r, d_spans[0], d_spans[1])
+        try:
+            n, n_bytes, _ = ctx.fasta_parse_status()
+        except api.CirckitError as e:
+            if "FASTA parse error" in str(e):                   # as fasta_parse reports it
+                raise ValueError(str(e))
+            raise
+        if n == 0:
+            return b"", title, np.zeros(0, dtype=np.uint64)
+        d_rows = torch.empty(n << sp.log2_bins, dtype=torch.int64, device=dev)
+        capacity = n * p.n_bands
+        d_pair_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_pairs = torch.empty(2 * capacity, dtype=torch.int32, device=dev)
+        d_scores = torch.empty(2 * capacity, dtype=torch.int32, device=dev)
+        d_labels = torch.empty(n, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream().synchronize()
+        ctx.sketch_batch_device(d_data, d_offs, n, d_rows, params=sp)
+        ctx.cluster_candidates_device(d_rows, n, sp.log2_bins, d_pair_off, d_pairs, capacity, params=p)
+        n_pairs = ctx.cluster_candidates_status()              # the compare takes the number of pairs from the host
+        ctx.sketch_compare_device(d_rows, n, d_rows, n, sp.log2_bins, d_pairs, n_pairs, d_scores)
+        ctx.cluster_link_device(n, d_pairs, d_scores, n_pairs, d_labels, params=p)
+        d_kept = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=dev)
+        d_kept_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_src = torch.empty(n, dtype=torch.int64, device=dev)
+        d_dup = torch.empty((2, n), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream().synchronize()
+        ctx.uniq_compact_device(d_data, d_offs, n, d_labels, d_kept, d_kept_off, d_src, 0, d_dup[0], d_dup[1])
+        ctx.sketch_status()
+        ctx.sketch_compare_status()
+        n_clusters, _, _ = ctx.cluster_link_status()
+        m, kept_bytes = ctx.uniq_compact_status()
+        assert m == n_clusters
+        cap = n_text + kept_bytes + 2 * m + 16                 # every head lies in the text
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        d_out_off = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream().synchronize()
+        ctx.fasta_write_device(d_text, n_text, d_spans[0], n, m, d_out, cap, d_out_off, d_body=d_kept, d_body_offsets=d_kept_off, d_src=d_src, n_src=m)
+        total, _ = ctx.fasta_write_status()
+        fasta = d_out[:total].cpu().numpy().tobytes()
+        labels = d_labels.cpu().numpy().view(np.uint64).copy()
+        dup = d_dup[:, :n - m].cpu().numpy().view(np.uint64)
+        head = d_spans[0, :n].cpu().numpy().view(np.uint64)
+    words = {}
+
+    def word(i):
+        if i not in words:
+            words[i] = _word(text[int(head[i][0]):int(head[i][0] + head[i][1])])
+        return words[i]
+
+    table = title + b"".join(word(int(a)) + b"\t" + word(int(b)) + b"\n" for a, b in zip(dup[0], dup[1]))
+    return fasta, table, labels
+
+
+# ---------------------------------------------------------------------------------------------
+# python -m circkit_amd.cluster [-i INPUT] [-o OUT] [--table T] ...
+# ---------------------------------------------------------------------------------------------
+def _parser():
+    p = argparse.ArgumentParser(prog="python -m circkit_amd.cluster", description="Cluster circular records by their k-mer sketches; write one representative per cluster")
+    p.add_argument("-i", "--input", help="input FASTA file [default: stdin]")
+    p.add_argument("-o", "--output", help="output FASTA file of the representatives [default: stdout]")
+    p.add_argument("--k", type=int, default=21, help="k-mer length, 4 .. 32")
+    p.add_argument("--bins", type=int, default=256, help="bins of a sketch: a power of two, 16 .. 1024")
+    p.add_argument("--bands", type=int, default=64, help="bands of a row, 1 .. 64")
+    p.add_argument("--band-bins", type=int, default=2, help="bins of a band, 1 .. 16")
+    p.add_argument("--min-similarity", type=float, default=0.2, help="a pair links at match / filled of at least this")
+    p.add_argument("--table", help="member<TAB>representative for every record that is not its cluster's representative")
+    return p
+
+
+def main(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.bins < 1 or a.bins & (a.bins - 1):
+        p.error("--bins must be a power of two")
+    try:
+        if a.input is None:
+            text = sys.stdin.buffer.read()
+        else:
+            with open(a.input, "rb") as f:
+                text = f.read()
+    except OSError as e:
+        sys.stderr.write("Error: %s\n" % e)
+        return 1
+    try:
+        fasta, table, _ = cluster_fasta(text, k=a.k, log2_bins=a.bins.bit_length() - 1, n_bands=a.bands, band_bins=a.band_bins,
+                                        min_similarity=a.min_similarity)
+    except (ValueError, api.CirckitError) as e:
+        sys.stderr.write("Error: %s\n" % e)
+        return 1
+    if a.output is None:
+        sys.stdout.buffer.write(fasta)
+        sys.stdout.buffer.flush()
+    else:
+        with open(a.output, "wb") as f:
+            f.write(fasta)
+    if a.table is not None:
+        with open(a.table, "wb") as f:
+            f.write(table)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

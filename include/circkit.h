@@ -546,6 +546,76 @@ int circkit_sketch_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t*
 int circkit_sketch_compare(circkit_ctx* ctx, const uint64_t* sketch_a, uint64_t n_a, const uint64_t* sketch_b, uint64_t n_b,
                            uint32_t log2_bins, const uint32_t* pairs, uint64_t n_pairs, uint32_t* out);
 
+/* ---- clusters of circular records ---------------------------------------------------------------- */
+/* Nothing in the reference is replaced: `cluster` is the first open item of its roadmap.  This section is the definition: which
+ * pairs of records are worth a compare (LSH banding over the sketch rows), and which records belong together once the pairs are
+ * scored (single linkage).
+ * BAND KEYS.  Band b of record i covers bins [b * band_bins, (b + 1) * band_bins) of its row.  If any of them is
+ * CIRCKIT_SKETCH_EMPTY the band has no key.  Otherwise x = (b + 1) * 0x9e3779b97f4a7c15 mod 2^64, then for each bin in order
+ * x = fmix64(x ^ bin) (the fmix64 of the sketch section); the key is x, except that x == 2^64 - 1 means "no key", as the empty
+ * bin does.
+ * CANDIDATES.  rep(key) = the smallest record index that has that key in any band.  Record i proposes, band by band in
+ * ascending b, the pair (rep(key(i, b)), i) when rep < i and no earlier band of the same record proposed the same rep (the first
+ * band wins).  So a pair is (smaller, larger), a record proposes at most n_bands pairs, and the members of a bucket are paired
+ * with its first holder, not with each other.  The definition is in terms of equal KEYS: a collision of two keys behaves the
+ * same in every implementation.
+ * LINKING.  Over n_pairs pairs with the (match, filled) the compare wrote for each: a pair with an index >= n_records is
+ * INVALID (counted, skipped, nothing dereferenced); a pair with i == j is skipped before its scores are read and is neither
+ * invalid nor linked; any other pair LINKS when filled >= min_filled and ((uint64)match << 16) >= (uint64)min_similarity_q16 *
+ * filled.  labels[i] = the smallest record index in i's connected component of the linked pairs (single linkage); the order of
+ * the pairs does not reach the result.  Record i is a representative iff labels[i] == i, so the labels are a valid
+ * d_first_seen for circkit_uniq_compact_device with base_index = 0. */
+typedef struct circkit_cluster_params {
+    uint32_t n_bands;                        /* 1 .. 64 */
+    uint32_t band_bins;                      /* 1 .. 16; n_bands * band_bins <= 1 << log2_bins */
+    uint32_t min_similarity_q16;             /* 0 .. 65536: a pair links iff (match << 16) >= min_similarity_q16 * filled ... */
+    uint32_t min_filled;                     /* >= 1: ... and filled >= min_filled */
+    uint32_t reserved[2];                    /* 0 */
+} circkit_cluster_params;
+
+/* The candidate pairs of the rows d_sketch (uint64[n_records << log2_bins], what circkit_sketch_batch_device wrote) as a CSR by
+ * the later record (no counterpart in the reference: its roadmap's `cluster`).  Device pointers; the call only enqueues work on
+ * the ctx stream.
+ *   d_pair_offsets  uint64[n_records + 1], 8-byte aligned, always written in full ([0] = 0 also with n_records == 0)
+ *   d_pairs         uint32[2 * capacity], 4-byte aligned: d_pairs[2p], d_pairs[2p + 1] = pair p; record i's pairs lie in
+ *                   [d_pair_offsets[i], d_pair_offsets[i + 1]) in band order -- the layout circkit_sketch_compare_device takes
+ * As with circkit_orfs_batch_device, a record whose pairs do not all lie below `capacity` is not written; the offsets and the
+ * total are exact all the same, and circkit_cluster_candidates_status returns CIRCKIT_ERR_OOM.  capacity = n_records * n_bands
+ * always suffices.  The smallest record with an equal key comes from circkit_uniq_resolve_device over the n_records * n_bands
+ * keys: as after that call, the ctx's uniq table is private to this one until the next circkit_uniq_reset.  Parameters out of
+ * range, reserved != 0, n_bands * band_bins > 1 << log2_bins, log2_bins outside 4 .. 10, null buffers (d_pairs may be null with
+ * capacity 0), n_records >= 2^32 or n_records * n_bands >= 2^32 - 1, or an output that overlaps the sketch or the other output:
+ * INVALID_ARG, nothing enqueued, buffers and earlier totals unchanged.  The result is bit-identical from run to run. */
+int circkit_cluster_candidates_device(circkit_ctx* ctx, const uint64_t* d_sketch, uint64_t n_records, uint32_t log2_bins,
+                                      const circkit_cluster_params* params, uint64_t* d_pair_offsets, uint32_t* d_pairs,
+                                      uint64_t capacity);
+/* Waits for the most recent candidates call of this ctx (roadmap `cluster`, nothing replaced): *total_pairs =
+ * d_pair_offsets[n_records]; CIRCKIT_ERR_OOM when that is more than the capacity it was given, or when circkit_uniq_status
+ * reports keys that found no slot (their bands proposed nothing).  The total is this call's own, whatever other unit ran in
+ * between. */
+int circkit_cluster_candidates_status(circkit_ctx* ctx, uint64_t* total_pairs);
+/* Single linkage over scored pairs (roadmap `cluster`, nothing replaced): d_pairs and d_scores are uint32[2 * n_pairs] (what the
+ * candidates and circkit_sketch_compare_device wrote, or any other list: either orientation, duplicates and self pairs are
+ * fine), d_labels uint64[n_records], 8-byte aligned, always written in full.  n_bands and band_bins of the parameters are
+ * checked and not used.  Device pointers; the call only enqueues.  Parameters out of range, n_records >= 2^32, null buffers
+ * with work, or d_labels overlapping an input: INVALID_ARG, nothing enqueued.  n_records == 0 and n_pairs == 0 are valid.  The
+ * labels are bit-identical from run to run. */
+int circkit_cluster_link_device(circkit_ctx* ctx, uint64_t n_records, const uint32_t* d_pairs, const uint32_t* d_scores,
+                                uint64_t n_pairs, const circkit_cluster_params* params, uint64_t* d_labels);
+/* Waits for the most recent link of this ctx (device or host form; roadmap `cluster`, nothing replaced): *n_clusters = the
+ * records with labels[i] == i, *n_linked = the pairs that passed the threshold, *n_invalid = the invalid pairs;
+ * CIRCKIT_ERR_INVALID_ARG when there was any, after the valid pairs were applied.  The totals are the link's own. */
+int circkit_cluster_link_status(circkit_ctx* ctx, uint64_t* n_clusters, uint64_t* n_linked, uint64_t* n_invalid);
+/* The whole chain with HOST buffers on one stream (roadmap `cluster`, nothing replaced): copy in, circkit_sketch_batch_device,
+ * the candidates with capacity n_records * n_bands, one wait for their number, circkit_sketch_compare_device, the link, copy the
+ * labels (uint64[n_records]) home, synchronize; *n_clusters (nullable) = the number of representatives.  offsets[0] must be 0
+ * and the offsets must not decrease; a record of 2^31 symbols or more is refused from the offsets alone: CIRCKIT_ERR_TOO_LONG,
+ * nothing computed.  The staging is the ctx's and only grows; the ctx's uniq table is private to the call until the next
+ * circkit_uniq_reset. */
+int circkit_cluster_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                          const circkit_sketch_params* sketch, const circkit_cluster_params* params, uint64_t* labels,
+                          uint64_t* n_clusters);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
