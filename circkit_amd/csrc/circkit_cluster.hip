@@ -11,7 +11,8 @@
 // A link is three: cluster_init_kernel (parent[i] = i), cluster_link_kernel (one lane per pair, striding: threshold and union),
 // cluster_flatten_kernel (labels and the number of roots).  No kernel uses LDS beyond the scan's and no workgroup waits for another.
 // The totals of either kind are the unit's own: they stay in device memory and are copied to page-locked memory behind the
-// work, and circkit_cluster_candidates_status / circkit_cluster_link_status answer from them whatever other unit ran in between.
+// work, and circkit_cluster_candidates_status / circkit_cluster_link_status answer from them whatever other unit ran in between:
+// the overflow count of the candidates' resolve is copied into their totals behind the resolve, one 4-byte copy on the stream.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(LINK_WG) void cluster_flatten_kernel(Link L)
 struct ClusterState {
     ck_totals cand;                  // [C_WORDS], of the most recent candidates call; both made with the state
     ck_totals link;                  // [L_WORDS], of the most recent link
-    bool any_cand = false, any_link = false, resolved = false;
+    bool any_cand = false, any_link = false;
     uint64_t capacity = 0;           // of the most recent candidates call
     uint64_t* d_keys = nullptr; uint64_t cap_keys = 0;          // n_records * n_bands (grow only, as everything below)
     uint64_t* d_first = nullptr; uint64_t cap_first = 0;
@@ -192,6 +193,10 @@ int launch_candidates(circkit_ctx* c, ClusterState* S, const uint64_t* d_sketch,
         hipLaunchKernelGGL(cluster_keys_kernel, dim3(grid_of(n_keys, KEYS_WG, KEYS_MAX_GRID)), dim3(KEYS_WG), 0, st, K);
         CK_HIP(c, hipGetLastError());
         if ((rc = circkit_uniq_resolve_device(c, S->d_keys, n_keys, 0, S->d_first, nullptr))) return rc;
+        // the resolve's overflow count while it is still this call's: the table is anybody's after the next circkit_uniq_reset
+        const uint32_t* d_overflow;
+        if ((rc = ck_uniq_overflow_word(c, &d_overflow))) return rc;
+        CK_HIP(c, hipMemcpyAsync(S->cand.d + ck_cluster::C_OVERFLOW, d_overflow, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(cluster_count_kernel, dim3(grid_of(n, EMIT_WAVES, EMIT_MAX_GRID)), dim3(64 * EMIT_WAVES), 0, st, E);
         hipLaunchKernelGGL(cluster_tile_sums_kernel, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_pair_offsets + 1, n, S->d_sums);
     }
@@ -203,7 +208,6 @@ int launch_candidates(circkit_ctx* c, ClusterState* S, const uint64_t* d_sketch,
     CK_HIP(c, hipGetLastError());
     if ((rc = ck_totals_fetch(c, &S->cand, C_WORDS))) return rc;
     S->capacity = capacity;
-    S->resolved = n != 0;
     S->any_cand = true;
     return CIRCKIT_OK;
 }
@@ -278,7 +282,9 @@ int circkit_cluster_candidates_status(circkit_ctx* c, uint64_t* total_pairs)
     CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     const uint64_t total = S->any_cand ? S->cand.h[ck_cluster::C_TOTAL] : 0;
     if (total_pairs) *total_pairs = total;
-    if (S->any_cand && S->resolved && (rc = circkit_uniq_status(c, nullptr))) return rc;     // keys that found no slot proposed nothing
+    const uint32_t overflow = S->any_cand ? (uint32_t)S->cand.h[ck_cluster::C_OVERFLOW] : 0;      // of this call's own resolve
+    if (overflow)                                                                                // keys that found no slot proposed nothing
+        return ck_fail(c, CIRCKIT_ERR_OOM, "uniq table overflow: %u key(s) found no slot (more distinct keys than circkit_uniq_reset sized it for)", overflow);
     return check_candidates(c, total, S->any_cand ? S->capacity : 0);
 }
 

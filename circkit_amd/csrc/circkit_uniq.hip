@@ -505,6 +505,16 @@ int uniq_size(circkit_ctx* c, UniqState* S, uint64_t expected_keys)
 
 }  // namespace
 
+// ck_ctx.h's: the overflow word for a unit that keeps the count of its own resolve
+int ck_uniq_overflow_word(circkit_ctx* c, const uint32_t** out)
+{
+    UniqState* S;
+    const int rc = uniq_state(c, &S);
+    if (rc) return rc;
+    *out = &S->d_words->overflow;
+    return CIRCKIT_OK;
+}
+
 extern "C" {
 
 int circkit_uniq_reset(circkit_ctx* c, uint64_t expected_keys)

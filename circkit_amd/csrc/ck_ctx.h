@@ -31,6 +31,11 @@ inline int ck_ctx_fail(circkit_ctx* c, int code, const char* msg) { return ck_fa
 enum ck_unit { CK_UNIT_ORFS, CK_UNIT_MONOMERIZE, CK_UNIT_UNIQ, CK_UNIT_UNIQ_COMPACT, CK_UNIT_WINDOWS, CK_UNIT_FASTA, CK_UNIT_FASTA_WRITE, CK_UNIT_SKETCH, CK_UNIT_CLUSTER, CK_N_UNITS };
 void** ck_ctx_slot(circkit_ctx* c, ck_unit unit, void (*release)(void*));
 
+// The uniq unit's overflow word on the device (circkit_uniq.hip): the records whose key found no slot since the table was last
+// cleared, 32 bits.  A unit that runs circkit_uniq_resolve_device for its own ends copies the word behind the resolve, on the ctx
+// stream, so that its status answers for its own resolve whatever uses the table afterwards.  *out stays valid for the ctx's life.
+int ck_uniq_overflow_word(circkit_ctx* c, const uint32_t** out);
+
 // A device buffer of a unit's state that only grows: *p holds at least `want` elements afterwards (its contents are not kept).
 template <typename T>
 int ck_grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)

@@ -26,7 +26,8 @@ constexpr uint64_t NO_KEY = ~0ull;
 constexpr uint64_t GOLDEN = 0x9e3779b97f4a7c15ull;
 constexpr uint32_t N_BANDS_MAX = 64, BAND_BINS_MAX = 16;
 constexpr uint32_t SCAN_WG = 256, SCAN_ITEMS = 2, SCAN_TILE = SCAN_WG * SCAN_ITEMS;      // of the scan of the records' pair counts
-enum { C_TOTAL, C_WORDS };                               // the totals of a candidates call, in device memory
+enum { C_TOTAL, C_OVERFLOW, C_WORDS };                   // the totals of a candidates call, in device memory: the pairs; the keys
+                                                         // of its own resolve that found no slot (the low 32 bits)
 enum { L_CLUSTERS, L_LINKED, L_INVALID, L_WORDS };       // the totals of a link
 
 // The 32-bit accesses to the parent array while other workgroups change it.  A read goes past this CU's L1 (an agent-scope

@@ -590,9 +590,9 @@ int circkit_cluster_candidates_device(circkit_ctx* ctx, const uint64_t* d_sketch
                                       const circkit_cluster_params* params, uint64_t* d_pair_offsets, uint32_t* d_pairs,
                                       uint64_t capacity);
 /* Waits for the most recent candidates call of this ctx (roadmap `cluster`, nothing replaced): *total_pairs =
- * d_pair_offsets[n_records]; CIRCKIT_ERR_OOM when that is more than the capacity it was given, or when circkit_uniq_status
- * reports keys that found no slot (their bands proposed nothing).  The total is this call's own, whatever other unit ran in
- * between. */
+ * d_pair_offsets[n_records]; CIRCKIT_ERR_OOM when that is more than the capacity it was given, or when keys of the call's own
+ * resolve found no slot (their bands proposed nothing).  The total and that count are this call's own, taken behind its resolve:
+ * whatever other unit ran in between, a later use of the ctx's uniq table and its circkit_uniq_status included. */
 int circkit_cluster_candidates_status(circkit_ctx* ctx, uint64_t* total_pairs);
 /* Single linkage over scored pairs (roadmap `cluster`, nothing replaced): d_pairs and d_scores are uint32[2 * n_pairs] (what the
  * candidates and circkit_sketch_compare_device wrote, or any other list: either orientation, duplicates and self pairs are

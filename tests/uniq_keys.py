@@ -36,6 +36,11 @@ def bucket_log2(n):
     return log2b
 
 
+def bkt_of(h, log2b):
+    """the bucket of a key in a bucketed resolve of 2^log2b buckets: its top log2b bits"""
+    return (np.asarray(h, dtype=np.uint64) >> np.uint64(64 - log2b)).astype(np.int64)
+
+
 def _distinct(rng, n, draw):
     """n distinct values of draw(k) (k values per call), in a seeded random order"""
     got = np.empty(0, dtype=np.uint64)
