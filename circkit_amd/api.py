@@ -108,6 +108,11 @@ SIGNATURES = {
     "circkit_cluster_link_device": (_i, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "circkit_cluster_link_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 3),
     "circkit_cluster_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64)]),
+    "circkit_sketch_anchors_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "circkit_prealign_pairs_device": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "circkit_prealign_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 2),
+    "circkit_prealign_pairs_of_labels_device": (_i, [_vp, _vp, _u64, _vp]),
+    "circkit_prealign_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -176,6 +181,22 @@ def cluster_params(n_bands=64, band_bins=2, min_similarity=0.2, min_filled=8):
     q = int(round(float(min_similarity) * 65536))
     p.n_bands, p.band_bins, p.min_filled = int(n_bands), int(band_bins), int(min_filled)
     p.min_similarity_q16 = q if 0 <= q < 2 ** 32 else 2 ** 32 - 1
+    return p
+
+
+# circkit_prealign_params / CIRCKIT_ANCHOR_NONE (include/circkit.h)
+ANCHOR_NONE = 0xFFFFFFFF
+
+
+class PrealignParams(ctypes.Structure):
+    _fields_ = [("k", _u32), ("log2_bins", _u32), ("min_votes", _u32), ("reserved", _u32)]
+
+
+def prealign_params(k=21, log2_bins=8, min_votes=4):
+    """circkit_prealign_params from Python values: the k and log2_bins the sketch and its anchors were made with; a pair is
+    aligned when at least min_votes (>= 1) shared bins agree on one rotation and strand.  The library checks the ranges."""
+    p = PrealignParams()
+    p.k, p.log2_bins, p.min_votes = int(k), int(log2_bins), int(min_votes)
     return p
 
 
@@ -860,6 +881,48 @@ class Context:
                                                     _ptr(labels) if n else None, ctypes.byref(m)))
         return labels, m.value
 
+    # -- pre-alignment of circular records -----------------------------------------------------------
+    def sketch_anchors_device(self, d_bytes, d_offsets, n_records, d_out_sketch, d_out_anchors, d_out_n_kmers=None, params=None, **kw):
+        """Enqueues circkit_sketch_anchors_device: sketch_batch_device that also writes d_out_anchors (uint32[n_records << log2_bins],
+        device): 2 * start + strand of the k-mer each bin holds, ANCHOR_NONE under an empty bin.  sketch_status() waits."""
+        p = params if params is not None else sketch_params(**kw)
+        self._check(self._lib.circkit_sketch_anchors_device(self._h, _ptr(d_bytes), _ptr(d_offsets), int(n_records), ctypes.byref(p),
+                                                            _ptr(d_out_sketch), _ptr(d_out_n_kmers), _ptr(d_out_anchors)))
+
+    def prealign_pairs_device(self, d_sketch, d_anchors, d_offsets, n_records, d_pairs, n_pairs, d_windows, d_scores, params=None, **kw):
+        """Enqueues circkit_prealign_pairs_device: window p of d_windows (WINDOW_DTYPE, device) rotates and flips record
+        d_pairs[2p + 1] onto record d_pairs[2p]; d_scores[2p], d_scores[2p + 1] = (votes, matches).  params: a prealign_params()
+        result, or its keywords.  prealign_status() waits."""
+        p = params if params is not None else prealign_params(**kw)
+        self._check(self._lib.circkit_prealign_pairs_device(self._h, _ptr(d_sketch), _ptr(d_anchors), _ptr(d_offsets), int(n_records), ctypes.byref(p),
+                                                            _ptr(d_pairs), int(n_pairs), _ptr(d_windows), _ptr(d_scores)))
+
+    def prealign_status(self):
+        """Waits for the last prealign pairs call; returns (aligned pairs, invalid pairs).  Raises CirckitError (INVALID_ARG) when
+        a pair named a record that does not exist."""
+        a, bad = _u64(0), _u64(0)
+        self._check(self._lib.circkit_prealign_status(self._h, ctypes.byref(a), ctypes.byref(bad)))
+        return a.value, bad.value
+
+    def prealign_pairs_of_labels_device(self, d_labels, n_records, d_pairs):
+        """Enqueues circkit_prealign_pairs_of_labels_device: d_pairs[2i], d_pairs[2i + 1] = (d_labels[i], i) (uint32, device)."""
+        self._check(self._lib.circkit_prealign_pairs_of_labels_device(self._h, _ptr(d_labels), int(n_records), _ptr(d_pairs)))
+
+    def prealign_batch(self, data, offsets, pairs, k=21, log2_bins=8, seed=0, min_votes=4):
+        """The windows and scores of the pairs (a, b) of a host CSR batch: (windows, scores) with windows an array of WINDOW_DTYPE
+        that windows_gather takes as it is and scores an (n_pairs, 2) uint32 array of (votes, matches)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        sp = sketch_params(k=k, log2_bins=log2_bins, seed=seed)
+        n, m = len(offsets) - 1, len(pairs)
+        windows = np.zeros(m, dtype=WINDOW_DTYPE)
+        scores = np.zeros((m, 2), dtype=np.uint32)
+        self._check(self._lib.circkit_prealign_batch(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, ctypes.byref(sp),
+                                                     _ptr(pairs) if m else None, m, int(min_votes), _ptr(windows) if m else None,
+                                                     _ptr(scores) if m else None))
+        return windows, scores
+
     def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
         """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
         import torch
@@ -1203,6 +1266,44 @@ def cluster_batch(seqs, k=21, log2_bins=8, seed=0, **cluster):
     offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
     data = np.frombuffer(b"".join(seqs), dtype=np.uint8)
     return default_context().cluster_batch(data, offsets, k=k, log2_bins=log2_bins, seed=seed, **cluster)
+
+
+def _csr_of(seqs):
+    seqs = [bytes(s) for s in seqs]
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    return np.frombuffer(b"".join(seqs), dtype=np.uint8), offsets
+
+
+def sketch_anchors(seqs, k=21, log2_bins=8, seed=0):
+    """sketch_batch with the anchors: (rows, counts, anchors), anchors an (n, 1 << log2_bins) uint32 array holding 2 * start +
+    strand of the k-mer every bin keeps (the smallest start), ANCHOR_NONE under an empty bin."""
+    import torch
+    data, offsets = _csr_of(seqs)
+    ctx = default_context()
+    n, bins = len(offsets) - 1, 1 << int(log2_bins)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(dev):
+        d_data = torch.from_numpy(data.copy()).to(dev) if len(data) else torch.zeros(1, dtype=torch.uint8, device=dev)
+        d_offs = torch.from_numpy(offsets.view(np.int64)).to(dev)
+        d_rows = torch.empty(max(n * bins, 1), dtype=torch.int64, device=dev)
+        d_anchors = torch.empty(max(n * bins, 1), dtype=torch.int32, device=dev)
+        d_counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream().synchronize()             # the copies are torch's, the kernels the ctx stream's
+        ctx.sketch_anchors_device(d_data, d_offs, n, d_rows, d_anchors, d_counts, k=k, log2_bins=log2_bins, seed=seed)
+        ctx.sketch_status()
+        rows = d_rows[:n * bins].cpu().numpy().view(np.uint64).reshape(n, bins)
+        counts = d_counts[:n].cpu().numpy().view(np.uint32)
+        anchors = d_anchors[:n * bins].cpu().numpy().view(np.uint32).reshape(n, bins)
+    return rows, counts, anchors
+
+
+def prealign_batch(seqs, pairs, k=21, log2_bins=8, seed=0, min_votes=4):
+    """For every pair (a, b) of a list of normalized records (bytes), the window that rotates and flips b onto a, and
+    (votes, matches): (windows, scores).  The windows are a WINDOW_DTYPE array that windows_gather takes as it is; a pair with
+    fewer than min_votes agreeing bins gets the identity window."""
+    data, offsets = _csr_of(seqs)
+    return default_context().prealign_batch(data, offsets, pairs, k=k, log2_bins=log2_bins, seed=seed, min_votes=min_votes)
 
 
 def orf_proteins(data, offsets, include_stop=False, **kw):

@@ -5,6 +5,8 @@
 //   sketch_short_kernel   one wave per record (striding): the row and count of a record of up to SKETCH_SEG symbols; a longer one gets
 //                         an EMPTY row and count 0 and is appended to the ctx's list, or counted as unprocessed from 2^31 symbols on
 //   sketch_long_kernel    a fixed grid over that list: the spans of every long record, merged into its row by the global minimum
+// With anchors (circkit_sketch_anchors_device, the "pre-alignment" section) the first is anchors_short_kernel, which writes the anchor
+// rows too, and a third follows: anchors_long_kernel, the same grid over the same list once the long rows are final.
 // A compare is one launch: sketch_compare_kernel, one wave per pair (striding).
 // The LDS of the first two is sized at the launch: SKETCH_WAVES slices of sketch.h's lds_words(log2_bins) 64-bit words.
 // The totals of either kind are the unit's own: they stay in device memory and are copied to page-locked memory behind the work,
@@ -17,6 +19,7 @@
 #include "ck_ctx.h"
 #include "sketch.h"
 
+using ck_sketch::Anchors;
 using ck_sketch::Compare;
 using ck_sketch::Sketch;
 using ck_sketch::SKETCH_WAVES;
@@ -41,6 +44,18 @@ __global__ __launch_bounds__(64 * SKETCH_WAVES) void sketch_long_kernel(Sketch S
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t sketch_lds[];
     ck_sketch::long_block(S, sketch_lds, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64 * SKETCH_WAVES) void anchors_short_kernel(Anchors A)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t sketch_lds[];
+    ck_sketch::anchors_short_block(A, sketch_lds, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64 * SKETCH_WAVES) void anchors_long_kernel(Anchors A)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t sketch_lds[];
+    ck_sketch::anchors_long_block(A, sketch_lds, blockIdx.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(64 * COMPARE_WAVES) void sketch_compare_kernel(Compare C)
@@ -101,9 +116,9 @@ int check_params(circkit_ctx* c, const circkit_sketch_params* p)
     return CIRCKIT_OK;
 }
 
-// the two launches and the copy of the totals; the arguments are checked
+// the two launches (three with anchors) and the copy of the totals; the arguments are checked
 int launch_sketch(circkit_ctx* c, SketchState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const circkit_sketch_params& p,
-                  uint64_t* d_out, uint32_t* d_counts)
+                  uint64_t* d_out, uint32_t* d_counts, uint32_t* d_anchors = nullptr)
 {
     int rc;
     if ((rc = ck_grow(c, &S->d_long, &S->cap_long, n ? n : 1))) return rc;
@@ -117,8 +132,18 @@ int launch_sketch(circkit_ctx* c, SketchState* S, const uint8_t* d_bytes, const 
         K.long_list = S->d_long; K.totals = S->totals.d;
         const uint64_t blocks = (n + SKETCH_WAVES - 1) / SKETCH_WAVES;
         const size_t lds = (size_t)SKETCH_WAVES * ck_sketch::lds_words(p.log2_bins) * sizeof(uint64_t);
-        hipLaunchKernelGGL(sketch_short_kernel, dim3((uint32_t)(blocks > SHORT_MAX_GRID ? SHORT_MAX_GRID : blocks)), dim3(64 * SKETCH_WAVES), lds, st, K);
-        hipLaunchKernelGGL(sketch_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), lds, st, K);
+        const dim3 short_grid((uint32_t)(blocks > SHORT_MAX_GRID ? SHORT_MAX_GRID : blocks));
+        if (d_anchors) {
+            Anchors A;
+            A.S = K; A.out_anchor = d_anchors;
+            const size_t alds = (size_t)SKETCH_WAVES * ck_sketch::anchors_lds_words(p.log2_bins) * sizeof(uint64_t);
+            hipLaunchKernelGGL(anchors_short_kernel, short_grid, dim3(64 * SKETCH_WAVES), alds, st, A);
+            hipLaunchKernelGGL(sketch_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), lds, st, K);
+            hipLaunchKernelGGL(anchors_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), alds, st, A);
+        } else {
+            hipLaunchKernelGGL(sketch_short_kernel, short_grid, dim3(64 * SKETCH_WAVES), lds, st, K);
+            hipLaunchKernelGGL(sketch_long_kernel, dim3(LONG_GRID), dim3(64 * SKETCH_WAVES), lds, st, K);
+        }
         CK_HIP(c, hipGetLastError());
     }
     if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
@@ -194,6 +219,28 @@ int circkit_sketch_batch_device(circkit_ctx* c, const uint8_t* d_bytes, const ui
     SketchState* S;
     if ((rc = state(c, &S))) return rc;
     return launch_sketch(c, S, d_bytes, d_offsets, n_records, *params, d_out_sketch, d_out_n_kmers);
+}
+
+int circkit_sketch_anchors_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records, const circkit_sketch_params* params,
+                                  uint64_t* d_out_sketch, uint32_t* d_out_n_kmers, uint32_t* d_out_anchors)
+{
+    if (!c) return CIRCKIT_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_params(c, params))) return rc;
+    if (n_records && (!d_bytes || !d_offsets || !d_out_sketch || !d_out_anchors)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (((uintptr_t)d_out_sketch & 7u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_out_n_kmers & 3u) || ((uintptr_t)d_out_anchors & 3u))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_offsets and d_out_sketch must be 8-byte aligned, d_out_n_kmers and d_out_anchors 4-byte aligned");
+    if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
+    const uint64_t row_bytes = (n_records << params->log2_bins) * sizeof(uint64_t), anchor_bytes = row_bytes / 2,
+                   off_bytes = (n_records + 1) * sizeof(uint64_t), count_bytes = n_records * sizeof(uint32_t);
+    if (overlap(d_out_sketch, row_bytes, d_offsets, off_bytes) || overlap(d_out_n_kmers, count_bytes, d_offsets, off_bytes) ||
+        overlap(d_out_sketch, row_bytes, d_out_n_kmers, count_bytes) || overlap(d_out_anchors, anchor_bytes, d_offsets, off_bytes) ||
+        overlap(d_out_anchors, anchor_bytes, d_out_sketch, row_bytes) || overlap(d_out_anchors, anchor_bytes, d_out_n_kmers, count_bytes))
+        return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_sketch / d_out_n_kmers / d_out_anchors overlap the offsets or each other");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    SketchState* S;
+    if ((rc = state(c, &S))) return rc;
+    return launch_sketch(c, S, d_bytes, d_offsets, n_records, *params, d_out_sketch, d_out_n_kmers, d_out_anchors);
 }
 
 int circkit_sketch_status(circkit_ctx* c, uint64_t* n_valid_kmers_total, uint32_t* n_unprocessed)

@@ -616,6 +616,72 @@ int circkit_cluster_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t
                           const circkit_sketch_params* sketch, const circkit_cluster_params* params, uint64_t* labels,
                           uint64_t* n_clusters);
 
+/* ---- pre-alignment of circular records ----------------------------------------------------------- */
+/* Nothing in the reference is replaced: `prealign` is the second open item of its roadmap.  The members of a cluster were each
+ * cut at an arbitrary position and read on an arbitrary strand; this section is the definition of the rotation and strand that
+ * put record b onto record a, from the k-mers their sketches share.
+ * ANCHORS.  For a record of n symbols and the parameters of the sketch section (k, log2_bins, seed), with `row` its sketch:
+ * anchor[b] = 2 * p + o, where p is the SMALLEST start whose valid cyclic k-mer has h == row[b], and o = (r < f) for the k-mer at
+ * that start: its reverse complement packs smaller, so the canonical form is the other strand's (a palindromic k-mer has o = 0).
+ * anchor[b] = CIRCKIT_ANCHOR_NONE where row[b] is CIRCKIT_SKETCH_EMPTY.  p < 2^31, so the word fits 32 bits.  The row is
+ * rotation-invariant and the anchors are not: that is the point.
+ * VOTES.  For a pair (a, b) with lengths n_a, n_b (0 < n_b < 2^31), every bin with row_a[bin] == row_b[bin] != EMPTY and both
+ * anchors != NONE is a MATCH, and votes: with pa, oa, pb, ob unpacked from the two anchors, s = oa ^ ob; if s == 1,
+ * pb = (n_b - pb - k) mod n_b (the same k-mer's start on revcomp(b)); start = (pb - pa) mod n_b, the mathematical (non-negative)
+ * modulus -- pa may exceed n_b; the vote is the 32-bit key (s << 31) | start.
+ * RESULT.  matches = the number of matching bins; votes = the largest number of equal keys, ties going to the SMALLEST key
+ * (strand 0 before strand 1, then the smaller start).  If votes >= min_votes the pair is ALIGNED and its window is
+ * {length n_b, record b, start, strand s, 0}: the circkit_window whose bytes put b's counterpart of a's position 0 first.
+ * Otherwise the window is the identity {n_b, b, 0, 0, 0}.  The scores (votes, matches) are always written.  A pair with
+ * a >= n_records or b >= n_records is INVALID: window {0, b, 0, 0, 0}, scores (0, 0), counted, and nothing it names is read.
+ * n_b == 0 gives {0, b, 0, 0, 0}; n_b >= 2^31 the identity window with that length; in both cases no bin votes (votes = 0) and
+ * matches is counted all the same.  A pair (i, i) is aligned at (0, 0) with votes == matches.  Anchors enter arithmetic only:
+ * nothing is dereferenced through them, and start < n_b holds by construction for any anchor values. */
+typedef struct circkit_prealign_params {
+    uint32_t k;                              /* 4 .. 32: the k the anchors were made with */
+    uint32_t log2_bins;                      /* 4 .. 10: of the rows and the anchors */
+    uint32_t min_votes;                      /* >= 1: a pair is aligned iff its votes reach this */
+    uint32_t reserved;                       /* 0 */
+} circkit_prealign_params;
+#define CIRCKIT_ANCHOR_NONE 0xFFFFFFFFu
+
+/* circkit_sketch_batch_device that writes the anchors too (no counterpart in the reference: its roadmap's `prealign`): the
+ * contract is that call's, and the rows and counts are bit-identical to what it writes.  In addition
+ *   d_out_anchors  uint32[n_records << log2_bins], 4-byte aligned, written in full: CIRCKIT_ANCHOR_NONE for all-EMPTY rows and
+ *                  for records that are not processed
+ * A null d_out_anchors with records, or one that overlaps the offsets or another output: INVALID_ARG, nothing enqueued.
+ * circkit_sketch_status answers for this call as for "the most recent sketch".  Bit-identical from run to run. */
+int circkit_sketch_anchors_device(circkit_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
+                                  const circkit_sketch_params* params, uint64_t* d_out_sketch, uint32_t* d_out_n_kmers,
+                                  uint32_t* d_out_anchors);
+/* The window and scores of every pair (roadmap `prealign`, nothing replaced).  d_sketch and d_anchors are what
+ * circkit_sketch_anchors_device wrote for the batch whose offsets are d_offsets (uint64[n_records + 1]; only the lengths are
+ * read); d_pairs is uint32[2 * n_pairs] in the compare's layout: the candidates, circkit_prealign_pairs_of_labels_device or any
+ * other list.  d_windows: n_pairs circkit_window, 8-byte aligned, what circkit_windows_gather_device takes; d_scores:
+ * uint32[2 * n_pairs], (votes, matches).  Device pointers; the call only enqueues.  k or log2_bins out of the sketch's range,
+ * min_votes == 0, reserved != 0, null buffers with work, n_records >= 2^32, or an output overlapping an input or the other
+ * output: INVALID_ARG, nothing enqueued, buffers and earlier totals unchanged.  n_pairs == 0 and n_records == 0 are valid. */
+int circkit_prealign_pairs_device(circkit_ctx* ctx, const uint64_t* d_sketch, const uint32_t* d_anchors, const uint64_t* d_offsets,
+                                  uint64_t n_records, const circkit_prealign_params* params, const uint32_t* d_pairs,
+                                  uint64_t n_pairs, circkit_window* d_windows, uint32_t* d_scores);
+/* Waits for the most recent pairs call of this ctx (device or host form; roadmap `prealign`, nothing replaced): *n_aligned = its
+ * aligned pairs, *n_invalid = its invalid pairs; CIRCKIT_ERR_INVALID_ARG when there was any, after the valid pairs were written.
+ * The totals are the call's own, whatever other unit ran in between. */
+int circkit_prealign_status(circkit_ctx* ctx, uint64_t* n_aligned, uint64_t* n_invalid);
+/* Pair i = (d_labels[i], i) for the labels of circkit_cluster_link_device (roadmap `prealign`, nothing replaced): every record
+ * against its representative, d_pairs uint32[2 * n_records].  A label of 2^32 or more is written as 0xFFFFFFFF, which the pairs
+ * call counts as invalid.  Device pointers (d_labels 8-byte, d_pairs 4-byte aligned); only enqueues.  Null buffers with records,
+ * n_records >= 2^32 or overlapping buffers: INVALID_ARG, nothing enqueued. */
+int circkit_prealign_pairs_of_labels_device(circkit_ctx* ctx, const uint64_t* d_labels, uint64_t n_records, uint32_t* d_pairs);
+/* The chain with HOST buffers on one stream (roadmap `prealign`, nothing replaced): copy in, circkit_sketch_anchors_device,
+ * circkit_prealign_pairs_device with (sketch->k, sketch->log2_bins, min_votes), copy the windows (n_pairs) and scores
+ * (uint32[2 * n_pairs]) home, synchronize.  offsets[0] must be 0 and the offsets must not decrease; a record of 2^31 symbols or
+ * more is refused from the offsets alone: CIRCKIT_ERR_TOO_LONG, nothing computed.  Invalid pairs: CIRCKIT_ERR_INVALID_ARG after
+ * the valid ones were written.  The staging is the ctx's and only grows. */
+int circkit_prealign_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+                           const circkit_sketch_params* sketch, const uint32_t* pairs, uint64_t n_pairs, uint32_t min_votes,
+                           circkit_window* windows, uint32_t* scores);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
