@@ -9,7 +9,7 @@
 // after one barrier every wave pulls its record(s) out of the image: one aligned ds_read_b128 per lane, pack to
 // 2 bits, and the record's offset mod 16 is removed on the PACKED words (one DPP shift + one 64-bit shift).  Output
 // goes straight from registers to global memory.
-// Default geometry (circkit_hip.hip): 16 waves, one record each, two 16 KiB images -- what matters most is running
+// Default geometry (canon_config.h): 16 waves, one record each, two 16 KiB images -- what matters most is running
 // 32 waves per CU; deeper rings with fewer waves measured slower (Measured).
 #pragma once
 #include "canon_fast.h"
@@ -149,7 +149,7 @@ CK_DEV void canon_stream_wave_loop(const CanonArgs& a, const uint32_t* lut, uint
     static_assert(!GH || (HASH && !AUX && C::ROWS == 1 && C::GROUP <= 16), "the group merger takes up to 16 records of one packed word per 16 symbols");
     // GH with two records per wave: canon_pair.h -- one record per half-wave, both at once
     // ... and the bytes-only build of such a geometry as well (gh = PAIR_SCRATCH_DW dwords per record then): the build for batches of
-    // SHORT records (circkit_hip.hip MODE_SHORT -- a record of 300 symbols keeps 19 of a wave's 64 lanes busy, two of them 20 of 32
+    // SHORT records (canon_config.h MODE_SHORT -- a record of 300 symbols keeps 19 of a wave's 64 lanes busy, two of them 20 of 32
     // each: 20M x 200 b 6.14 -> 4.84 ms, 10M x 400 b 3.34 -> 2.68; from ~850 symbols on one record per wave is faster)
     constexpr bool PAIR_B = !HASH && !AUX && !ALPHA && C::ROWS == 1 && C::RPW == 2;
     constexpr bool PAIR = (GH && C::RPW == 2) || PAIR_B;
@@ -204,49 +204,22 @@ CK_DEV void canon_stream_wave_loop(const CanonArgs& a, const uint32_t* lut, uint
     uint32_t img_dw = 0, free_dw = (C::NBUF - 1) * C::BUF_DW, it = 0;
     const uint32_t pf_off = (t >> 5) * (C::GROUP * 8);
     uint32_t oor = (n_staged - 1u - gf) >> 31;                  // 1: the group to prefetch does not exist (both < 2^28)
-#ifdef CK_EXP_UNIFORM
-    uint64_t exp_a, exp_b;
-    sload_2u64(a.offsets, a.offsets + 1, exp_a, exp_b);
-    const uint32_t exp_len = (uint32_t)(exp_b - exp_a);
-#endif
     for (uint32_t g = block; g < n_staged; g += nblocks, ++it) {
         // one scalar round trip per iteration: the span of the group to prefetch and this wave's record offsets
         uint64_t s, e, o0, o1, o2;
-#ifdef CK_EXP_UNIFORM
-        // EXPERIMENT build only: offsets of a batch of equal-length records computed from the (runtime) length
-        { const uint64_t L = exp_len; s = (uint64_t)(oor ? 0 : gf) * C::GROUP * L; e = s + C::GROUP * L; o0 = (uint64_t)ra * L; o1 = o0 + L; o2 = o1 + L; }
-#elif defined(CK_EXP_FIXED1000)
-        // EXPERIMENT build only (tools/probe_variants.py): every record 1000 bytes, offsets computed instead of loaded -- an upper
-        // bound of what leaner scalar bookkeeping at the head of the loop could buy
-        s = (uint64_t)(oor ? 0 : gf) * C::GROUP * 1000; e = s + C::GROUP * 1000; o0 = (uint64_t)ra * 1000; o1 = o0 + 1000; o2 = o1 + 1000;
-#else
-#ifdef CK_STREAM_INDEXED
-        sload_group<(int)C::GROUP>(a.offsets + (uint64_t)(oor ? 0u : gf) * C::GROUP, a.offsets + ra, s, e, o0, o1, o2);
-#else
         sload_group<(int)C::GROUP>(oor ? a.offsets : p_grp, p_rec, s, e, o0, o1, o2);
-#endif
-#endif
 #ifdef CK_DEBUG_POISON
         stream_poison<C>(ring + free_dw);
-#endif
-#ifdef CK_EXP_DMA_SLEEP
-        if (!HASH) __builtin_amdgcn_s_sleep(CK_EXP_DMA_SLEEP);      // EXPERIMENT: the bytes-only build loses when its loads go out earlier -- does it gain when they go out later?
 #endif
         const StreamGroup fut = stream_issue<C>(a, sb, oor, s, e, ring + free_dw, c16);
         // the next iteration's group to prefetch
         gf += nblocks;
-#ifndef CK_STREAM_INDEXED
         p_grp += stride;
-#endif
         oor = (n_staged - 1u - gf) >> 31;
         if constexpr (PF) {
             // the offsets the next iteration loads: the span of that group -- its first offset (lanes 0..31) and the one behind
             // its last (lanes 32..63: the next 128 bytes) -- which are also the lines of this wave's record two iterations on
-#ifdef CK_STREAM_INDEXED
-            glds4_touch(ring + (C::LDS_DW - 64), a.offsets + (uint64_t)(oor ? 0u : gf) * C::GROUP, pf_off);
-#else
             glds4_touch(ring + (C::LDS_DW - 64), oor ? a.offsets : p_grp, pf_off);
-#endif
         }
         const uint32_t* img = ring + img_dw;
         uint32_t* slot = GH ? gh + ((it & 1) * C::GROUP + C::RPW * w) * GH_STRIDE_DW : PAIR_B ? gh + C::RPW * w * PAIR_SCRATCH_DW : nullptr;
@@ -374,9 +347,7 @@ CK_DEV void canon_stream_wave_loop(const CanonArgs& a, const uint32_t* lut, uint
         free_dw = img_dw;
         img_dw = img_dw + C::BUF_DW == C::NBUF * C::BUF_DW ? 0 : img_dw + C::BUF_DW;
         ra += nblocks * C::GROUP;
-#ifndef CK_STREAM_INDEXED
         p_rec += stride;
-#endif
     }
     if constexpr (GH) {
         if (it > 0 && w == ((it - 1) & (C::WPB - 1))) {             // the last group's hashes (behind the loop's final barrier)

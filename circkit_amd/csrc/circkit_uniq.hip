@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void uniq_keep_kernel(const uint64_t* __restri
 #ifndef CK_UNIQ_LOAD_PCT
 #define CK_UNIQ_LOAD_PCT 70       // circkit_uniq_reset sizes the table for at most this load with `expected_keys` distinct keys
 #endif
-constexpr int N_CU = 256;                                // (as in circkit_hip.hip, which sizes its own grids by it)
+constexpr int N_CU = 256;                                // (as in canon_config.h, by which the canonicalize unit sizes its own grids)
 constexpr unsigned UNIQ_GRID = N_CU * CK_UNIQ_BPC;       // the table kernels' grid, by 256 threads
 
 // the words the kernels report through and the partition step's scatter cursors: one small device allocation, zeroed when made

@@ -1,7 +1,8 @@
-// ck_ctx.h -- what a translation unit other than circkit_hip.hip may ask of the ctx (internal; not part of the C ABI).
+// ck_ctx.h -- what a translation unit may ask of the ctx (internal; not part of the C ABI).
 //
-// struct circkit_ctx lives in circkit_hip.hip and nothing outside that file names one of its fields.  The other units (one
-// circkit_*.hip per ck_unit below) enqueue on the ctx's stream, report through its error string and keep their own state behind
+// struct circkit_ctx is defined in ck_ctx_impl.h, which only circkit_hip.hip (the ctx's lifecycle) and circkit_canon.hip (the
+// canonicalize state, allocated with the ctx) include; nothing else names one of its fields.  The other units (one
+// circkit_*.hip per ck_unit below, and circkit_bench.hip) enqueue on the ctx's stream, report through its error string and keep their own state behind
 // one slot each, which circkit_ctx_destroy releases.  What that state is made of is here once: a grow-only device buffer
 // (ck_grow) and the totals of a unit's most recent call (ck_totals).
 #pragma once

@@ -138,6 +138,7 @@ void run_wave(void (*body)(void*), void* arg) { run_block(body, arg, 1); }
 #include "../../circkit_amd/csrc/canon_stream.h"
 #include "../../circkit_amd/csrc/canon_mixed.h"
 #include "../../circkit_amd/csrc/xxh3_core.h"
+#include "../../circkit_amd/csrc/canon_config.h"
 
 namespace {
 struct Launch { ck::CanonArgs a; uint32_t* lds; const uint32_t* lut; const uint32_t* lutn = nullptr; const uint32_t* lean_lutn = nullptr; uint32_t* blk_count; uint32_t block, nblocks, wib; bool all_records = false, alpha = false, solo = true, team4 = true; const uint32_t* htab = nullptr; };
@@ -405,4 +406,13 @@ extern "C" int64_t emu_seg_cover(uint64_t n, uint32_t nseg, uint32_t all_cap, ui
         ++used;
     }
     return next == n ? used : -1;
+}
+
+// batch_geometry (canon_config.h), the function launch_canon calls: out = G, cap, all_cap, taper_seg0, taper_log2.
+// per_step 0 / 1: the streaming kernel's own group size without / with index and strand, as launch_canon passes it.
+extern "C" void emu_batch_geometry(uint64_t n, uint64_t per_step, uint32_t out[5])
+{
+    if (per_step < 2) per_step = per_step ? StreamCAux::GROUP : StreamC::GROUP;
+    const BatchGeometry g = batch_geometry(n, per_step);
+    out[0] = g.G; out[1] = g.cap; out[2] = g.all_cap; out[3] = g.taper_seg0; out[4] = g.taper_log2;
 }

@@ -9,6 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "circkit_amd", "csrc")
 LIB = os.path.join(HERE, "libcirckit_hip_poison.so")
+# the ctx, the canonicalize path (the streaming loop the flag changes) and what a test batch is made with; no other unit
+UNITS = ["circkit_hip.hip", "circkit_canon.hip", "circkit_bench.hip", "fasta_host.cpp"]
 
 
 def build(force=False, negative_control=False):
@@ -24,5 +26,5 @@ def build(force=False, negative_control=False):
     hipcc = _hipcc()
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-inline-asm", "-DCK_DEBUG_POISON"] +
                           (["-DCK_DEBUG_POISON_BREAK"] if negative_control else []) +
-                          ["-o", lib, os.path.join(CSRC, "circkit_hip.hip"), os.path.join(CSRC, "fasta_host.cpp")])
+                          ["-o", lib] + [os.path.join(CSRC, s) for s in UNITS])
     return lib

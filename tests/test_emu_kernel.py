@@ -686,7 +686,7 @@ def test_mixed_kernel_with_fused_xxh3(with_n, hash_only):
 
 
 def _host_taper(n, G):
-    """launch_canon's sizing of the walking stages' segments (circkit_hip.hip): (all_cap, taper_seg0, taper_log2)."""
+    """launch_canon's sizing of the walking stages' segments (batch_geometry, canon_config.h), restated: (all_cap, taper_seg0, taper_log2)."""
     all_cap = -(-n // G)
     seg0 = log2 = 0
     if G >= 4096 and all_cap >= 16:
@@ -700,13 +700,27 @@ def _host_taper(n, G):
 
 
 def test_tapered_segments_tile_the_batch():
-    """seg_records: equal segments, then three generations of smaller ones -- every record in exactly one segment."""
+    """seg_records: equal segments, then three generations of smaller ones -- every record in exactly one segment.
+    And batch_geometry (canon_config.h, the function launch_canon calls, compiled for the CPU) agrees with the two restatements:
+    with _host_taper on the (n, G) cases below -- G follows from n and the records a workgroup takes per step, so each case is
+    asked with every per_step that gives its G; (131_071, 8191) and (50_000, 4095) have none (ceil(131_071 / 16) = 8192 and
+    ceil(131_071 / 17) = 7711; from 4096 records on G is at least 4096) and are asserted to have none -- and with
+    tests/launch_geometry.py on every count of GEOMETRY_COUNTS, without and with index / strand."""
     import ctypes
+    from tests import launch_geometry as LG
     lib = ctypes.CDLL(emu.build())
     lib.emu_seg_cover.restype = ctypes.c_int64
     lib.emu_seg_cover.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+    lib.emu_batch_geometry.restype = None
+    lib.emu_batch_geometry.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]
+
+    def shipped(n, per_step):
+        out = (ctypes.c_uint32 * 5)()
+        lib.emu_batch_geometry(n, per_step, out)
+        return tuple(out)                          # G, cap, all_cap, taper_seg0, taper_log2
     cases = [(1_000_000, 32768), (10_000_000, 32768), (999_983, 32768), (70_000, 4096), (65_536, 4096), (131_071, 8191),
              (5_000_000, 20_000), (524_288, 32768), (524_289, 32768), (100, 100), (50_000, 4095)]
+    reached = []
     for n, G in cases:
         cap, seg0, log2 = _host_taper(n, G)
         used = lib.emu_seg_cover(n, G, cap, seg0, log2)
@@ -714,6 +728,23 @@ def test_tapered_segments_tile_the_batch():
         if log2:
             gen = 1 << log2
             assert seg0 + 3 * gen == G and cap >> 3 >= 1
+        # per_step from 2 (0 and 1 name the streaming kernel's own) to where a batch is one workgroup's
+        steps = [p for p in range(2, min(n, 1024) + 1) if shipped(n, p)[0] == G]
+        for p in steps:
+            got = shipped(n, p)
+            assert got[2:] == (cap, seg0, log2), (n, G, p, got)
+            assert got[1] >= got[2] and got[1] >= p * -(-(-(-n // p)) // G)          # a list segment holds what a workgroup sees
+        if steps:
+            reached.append((n, G))
+    assert sorted(set(cases) - set(reached)) == [(50_000, 4095), (131_071, 8191)]
+    c = LG.source_constants()
+    for aux in (False, True):
+        for n in LG.GEOMETRY_COUNTS:
+            G, all_cap, tapered = LG.geometry(n, aux, c)
+            got = shipped(n, 1 if aux else 0)
+            assert (got[0], got[2], got[4] != 0) == (G, all_cap, tapered), (n, aux, got)
+            assert got[2:] == _host_taper(n, G), (n, aux, got)
+            assert lib.emu_seg_cover(n, got[0], got[2], got[3], got[4]) > 0, (n, aux, got)
     # no taper = the plain mapping
     assert lib.emu_seg_cover(1000, 10, 100, 0, 0) == 10
     assert lib.emu_seg_cover(1001, 10, 100, 0, 0) == -1

@@ -968,49 +968,9 @@ def test_batches_of_short_records_bytes_only_pair_build(ctx, O):
 
 
 # ---- batches at the streaming launch's geometry edges ----------------------------------------------------------------------
-# launch_canon (circkit_hip.hip) cuts a batch of n records into G workgroups of the streaming kernel (per_step records per
-# iteration: StreamC::GROUP = CK_STREAM_WPB * CK_STREAM_RPW, or StreamCAux::GROUP = WPB * RPW of StreamCfg<4, 4, 2, 1> when
-# index / strand are wanted), G = max(min(ceil(n / per_step), N_CU * CK_FAST_BPC), min(n, N_CU * 16)); the stages that walk
-# all records take all_cap = ceil(n / G) per segment, and when G >= 4096 and all_cap >= 2 << CK_TAPER_GENS the last
-# CK_TAPER_GENS generations of G / CK_TAPER_DIV segments taper off (canon_core.h seg_records) with all_cap raised until they
-# still hold n.  With the constants of this writing (16, 1, 4 * 2 = 8, 256, 128, 3, 16):
-#   G leaves its floor of 4096       n = 65 537 (bytes / + XXH3 / hash only)      n = 32 769 (+ index / strand)
-#   taper starts (all_cap 15 -> 16,  n = 61 441: 4096 segments, all_cap 18      n = 491 521: 32 768 segments, all_cap 18
-#   raised by the taper to 18)
-#   grid capped at 32 768 (one       n = 524 273 (524 288 = 32 768 * 16: every    n = 262 137
-#   workgroup walks several groups)  workgroup exactly one group)
-# _geometry() below restates that arithmetic from the constants in the sources, and the test asserts the counts still sit on
-# both sides of each edge: a change of those constants fails here and points back at this list.
-GEOMETRY_COUNTS = [32_768, 32_769, 61_440, 61_441, 61_442, 65_536, 65_537, 262_136, 262_137, 262_138, 491_520, 491_521, 491_522,
-                   524_272, 524_273, 524_288, 524_289, 1_000_003]
-
-
-def _hip_constants():
-    import re
-    src = os.path.join(os.path.dirname(GOLDEN), os.pardir, "circkit_amd", "csrc")
-    hip = open(os.path.join(src, "circkit_hip.hip")).read() + open(os.path.join(src, "canon_core.h")).read()
-    c = {k: int(re.search(r"#define %s (\d+)" % k, hip).group(1)) for k in ("CK_STREAM_WPB", "CK_STREAM_RPW", "CK_FAST_BPC", "CK_TAPER_GENS",
-                                                                             "CK_TAPER_DIV")}
-    c["N_CU"] = int(re.search(r"constexpr int N_CU = (\d+);", hip).group(1))
-    wpb, _, rpw, _ = map(int, re.search(r"using StreamCAux = ck::StreamCfg<(\d+), (\d+), (\d+), (\d+)>;", hip).groups())
-    c["AUX_GROUP"] = wpb * rpw
-    return c
-
-
-def _geometry(n, aux, c):
-    """(G, all_cap, tapered) of launch_canon for a batch of n records."""
-    per_step = c["AUX_GROUP"] if aux else c["CK_STREAM_WPB"] * c["CK_STREAM_RPW"]
-    G = max(min(-(-n // per_step), c["N_CU"] * c["CK_FAST_BPC"]), min(n, c["N_CU"] * 16))
-    all_cap, gens = -(-n // G), c["CK_TAPER_GENS"]
-    if not (G >= 4096 and all_cap >= 2 << gens):
-        return G, all_cap, False
-    log2 = 0
-    while (2 << log2) <= G // c["CK_TAPER_DIV"]:
-        log2 += 1
-    seg0 = G - gens * (1 << log2)
-    while seg0 * all_cap + (1 << log2) * sum(all_cap >> j for j in range(1, gens + 1)) < n:
-        all_cap += 1
-    return G, all_cap, True
+# tests/launch_geometry.py says where the edges are and restates batch_geometry's arithmetic (canon_config.h) from the constants
+# in the sources; tests/test_emu_kernel.py compares the shipped function with it.
+from tests.launch_geometry import GEOMETRY_COUNTS, geometry as _geometry, source_constants as _hip_constants      # noqa: E402
 
 
 def test_geometry_counts_straddle_the_launch_edges():

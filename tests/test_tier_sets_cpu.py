@@ -2,7 +2,7 @@
 (no triple is scaled: the slowest test of this file takes ~1.2 s on the build machine, the file ~7 s behind the emulator's build).
 
 tests/tier_sets.py derives every boundary from the restated predicates; here
-  * the restated constants and predicates are compared with the text of circkit_hip.hip / canon_core.h / canon_mixed.h,
+  * the restated constants and predicates are compared with the text of canon_config.h / circkit_canon.hip / canon_core.h / canon_mixed.h,
   * every record class's construction is proved from the records alone,
   * for every reachable triple of stage A, stage C (fed with what stage A's emulated workgroup deferred) and the two mixed builds
     one 4-wave workgroup runs with its LDS pre-filled with a pattern and a guard region behind the four slices

@@ -1,7 +1,7 @@
 """Record sets that sit ON the admission boundaries of the LDS stages, their teams, the mixed-length kernels and the scratch.
 
 Beyond the register and lean routines a record's route is decided by admission arithmetic: a predicate on its length n against
-a slice capacity, exact, without slack (canon_core.h canon_record / team_pass, circkit_hip.hip team_stage_block / launch_single,
+a slice capacity, exact, without slack (canon_core.h canon_record / team_pass, canon_kernels.h team_stage_block, circkit_canon.hip launch_single,
 canon_mixed.h canon_lean_record).  This module holds
   * the predicates and the capacity table restated in Python, with a reader of the same constants from the source text, so that
     the restated copy cannot drift unnoticed (tests/test_tier_sets_cpu.py),
@@ -91,7 +91,8 @@ def stage_cap(stage, route):
 
 def source_constants():
     """the same constants as the sources spell them (text, no compiler): name -> value, and the predicates' return expressions"""
-    hip = open(os.path.join(CSRC, "circkit_hip.hip")).read()
+    hip = open(os.path.join(CSRC, "canon_config.h")).read()
+    canon = open(os.path.join(CSRC, "circkit_canon.hip")).read()
     core = open(os.path.join(CSRC, "canon_core.h")).read()
     mixed = open(os.path.join(CSRC, "canon_mixed.h")).read()
 
@@ -109,7 +110,7 @@ def source_constants():
     c["TEAM_WAVES"] = int(one(hip, r"constexpr int TEAM_WAVES = (\d+);"))
     c["GSLICE1_DW"] = one(hip, r"GSLICE1_DW = ([^;]*);")
     c["worst_case_dw"] = one(hip, r"worst_case_dw\(uint64_t n\) \{ return ([^;]*); \}")
-    c["single_handover"] = one(hip, r"if \(n == 1 && ([^)]*\) / 16 \+ 2 <= TIER_DW\[0\])\)")
+    c["single_handover"] = one(canon, r"if \(n == 1 && ([^)]*\) / 16 \+ 2 <= TIER_DW\[0\])\)")
     c["LEAN_CAND"] = one(mixed, r"constexpr uint32_t (LEAN_CAND_MAX = \d+, LEAN_CAND_DW = [^;]*);")
     c["lean_strand_dw"] = one(mixed, r"lean_strand_dw\(uint32_t n\) \{ return ([^;]*); \}")
     c["lean_mask_dw"] = one(mixed, r"lean_mask_dw\(uint32_t n\) \{ return ([^;]*); \}")
