@@ -44,6 +44,9 @@ def lib():
     return _lib
 
 
+HIGH_LEAD = 1 << 30
+
+
 def tile_bytes():
     return int(lib().emu_compact_tile_bytes())
 
@@ -56,7 +59,9 @@ def compact(data, offsets, ends, full_len=None, in_shift=0, out_shift=0, lead=0,
             min_overlap_percent=None, keep_all=False):
     """decide + scan + the gather's workgroup body on a CSR batch: (out_data, out_offsets, out_src, kept_end).
     in_shift / out_shift: the payload / output pointer mod 16; lead: offsets[0] (canary bytes in front of the first record).
-    Canaries surround the payload and every output; the input is checked to be unchanged."""
+    Canaries surround the payload and every output; the input is checked to be unchanged.  A lead of HIGH_LEAD bytes and more
+    (the leads that put a payload across byte 2^32 of its buffer) takes a lazily reserved mapping: the lead region is neither
+    touched nor copied, canaries surround the payload only, and only that window is compared."""
     L = lib()
     data = np.ascontiguousarray(data, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -65,11 +70,18 @@ def compact(data, offsets, ends, full_len=None, in_shift=0, out_shift=0, lead=0,
     assert offsets[0] == 0 and len(ends) == n
     nb = len(data)
     offsets = offsets + np.uint64(lead)
-    raw = np.full(64 + in_shift + lead + nb + 64, IN_CANARY, dtype=np.uint8)
+    if lead >= HIGH_LEAD:
+        import mmap
+        raw = np.frombuffer(mmap.mmap(-1, 64 + in_shift + lead + nb + 64, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS | getattr(mmap, "MAP_NORESERVE", 0x4000)),
+                            dtype=np.uint8)
+    else:
+        raw = np.full(64 + in_shift + lead + nb + 64, IN_CANARY, dtype=np.uint8)
     skew = (-raw.ctypes.data) % 64 + in_shift
     pad = raw[skew:]
+    window = raw[skew + lead - 64:skew + lead + nb + 64] if lead >= HIGH_LEAD else raw
+    window[:] = IN_CANARY
     pad[lead:lead + nb] = data
-    before = raw.copy()
+    before = window.copy()
     raw_out = np.full(64 + out_shift + nb + 64, OUT_CANARY, dtype=np.uint8)
     oskew = (-raw_out.ctypes.data) % 64 + out_shift
     out = raw_out[oskew:]
@@ -85,7 +97,7 @@ def compact(data, offsets, ends, full_len=None, in_shift=0, out_shift=0, lead=0,
                                 kept[64:].ctypes.data, ctypes.byref(m))
     assert rc == 0, "the lanes of a wave disagree on the record their search found"
     m = m.value
-    assert np.array_equal(raw, before), "the compact wrote into its input"
+    assert np.array_equal(window, before), "the compact wrote into its input"
     B = int(out_off[64 + m])
     assert (raw_out[:oskew] == OUT_CANARY).all() and (out[B:] == OUT_CANARY).all(), "wrote outside [out, out + B)"
     assert (out_off[:64] == OFF_CANARY).all() and (out_off[64 + m + 1:] == OFF_CANARY).all(), "out_offsets written beyond entry m"

@@ -25,7 +25,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "circkit_amd", "cs
 
 def build():
     base = emu.build()
-    deps = [_SRC, base, os.path.join(_HERE, "wave_prims_emu.h")] + [os.path.join(_CSRC, f) for f in ("sketch.h", "wave_prims.h")]
+    deps = [_SRC, base, os.path.join(_HERE, "wave_prims_emu.h"), os.path.join(_HERE, "lead_block.h")] + [os.path.join(_CSRC, f) for f in ("sketch.h", "wave_prims.h")]
     if not os.path.exists(_BIN) or any(os.path.getmtime(d) > os.path.getmtime(_BIN) for d in deps):
         # the same UBSan + bounds flags as the emulator library, no recovery
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17"] + emu.SANITIZE + ["-o", _BIN, _SRC, "-L" + _HERE, "-l:libcanon_emu.so",

@@ -21,6 +21,7 @@ void run_block(void (*body)(void*), void* arg, int nwaves);            // tests/
 }}
 
 #include "../../circkit_amd/csrc/sketch.h"
+#include "lead_block.h"
 
 namespace {
 
@@ -74,10 +75,10 @@ int sketch_case(FILE* in, FILE* out, uint64_t c)
     if (!get(in, h, sizeof h)) { fprintf(stderr, "case %llu: short header\n", (unsigned long long)c); return 2; }
     const uint64_t n = h[0], nb = h[1], lead = h[2], bins = 1ull << h[5];
     std::vector<uint64_t> offsets(n + 1);
-    Block payload(h[3], lead + nb, IN_CANARY);
-    if (!get(in, offsets.data(), 8 * (n + 1)) || !get(in, payload.use() + lead, nb)) { fprintf(stderr, "case %llu: short body\n", (unsigned long long)c); return 2; }
+    ck_emu::LeadBlock payload(h[3], lead, nb, IN_CANARY);
+    if (!get(in, offsets.data(), 8 * (n + 1)) || !get(in, payload.payload(), nb)) { fprintf(stderr, "case %llu: short body\n", (unsigned long long)c); return 2; }
     for (uint64_t& o : offsets) o += lead;
-    const std::vector<uint8_t> before(payload.use(), payload.use() + lead + nb);
+    payload.keep();
     const std::vector<uint64_t> offsets_before = offsets;
 
     Block rows(0, n * bins * 8, OUT_CANARY), counts(0, n * 4, OUT_CANARY), list(0, n * 8, OUT_CANARY);
@@ -96,7 +97,7 @@ int sketch_case(FILE* in, FILE* out, uint64_t c)
         for (L.block = 0; L.block < L.grid; ++L.block) ck::emu::run_block(long_body, &L, (int)ck_sketch::SKETCH_WAVES);
     }
     uint64_t rc = RC_OK;
-    if (!payload.intact() || changed(before, payload.use()) || offsets != offsets_before || !rows.intact() || !counts.intact() ||
+    if (!payload.unchanged() || offsets != offsets_before || !rows.intact() || !counts.intact() ||
         !list.intact() || !lds.intact())
         rc = RC_CANARY;
     if (!h[9]) for (size_t i = 0; i < n * 4; ++i) if (counts.use()[i] != OUT_CANARY) rc = RC_CANARY;

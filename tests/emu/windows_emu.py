@@ -26,7 +26,7 @@ EXACT = 2 ** 64 - 1
 
 def build():
     base = emu.build()
-    deps = [_SRC, base, os.path.join(_HERE, "wave_prims_emu.h")] + \
+    deps = [_SRC, base, os.path.join(_HERE, "wave_prims_emu.h"), os.path.join(_HERE, "lead_block.h")] + \
         [os.path.join(_CSRC, f) for f in ("window_gather.h", "monomer_compact.h", "wave_prims.h")]
     if not os.path.exists(_BIN) or any(os.path.getmtime(d) > os.path.getmtime(_BIN) for d in deps):
         # the same UBSan + bounds flags as the emulator library, no recovery

@@ -4,7 +4,8 @@
 // effective_length() runs per window as the lengths kernel's lane runs it; the scan between the two is plain host code with
 // the same saturating sum (the scan kernels use no wave routine); gather_tile() runs as a workgroup of the product's
 // GATHER_WAVES waves per output tile, so a lane that skips a collective deadlocks its wave, and UBSan + bounds checks watch
-// every shift and access.  The payload and the output each lie in an exactly sized heap block between canaries.
+// every shift and access.  The payload and the output each lie in an exactly sized heap block between canaries; a lead of a GiB
+// and more puts the payload into a lazily reserved mapping instead (tests/emu/lead_block.h).
 //   windows_emu_main --constants          prints "TILE_BYTES GATHER_WAVES"
 //   windows_emu_main --of-records KIND BASES PERCENT_BITS N...   window_of_record() per length N, as the kernel's lane runs it: one
 //                                         line "length record start strand reserved" each (PERCENT_BITS: the f64's bits in hex)
@@ -22,6 +23,7 @@ void run_block(void (*body)(void*), void* arg, int nwaves);            // tests/
 }}
 
 #include "../../circkit_amd/csrc/window_gather.h"
+#include "lead_block.h"
 
 namespace {
 
@@ -102,13 +104,13 @@ int main(int argc, char** argv)
         const uint64_t n = h[0], m = h[1], nb = h[2], lead = h[3];
         std::vector<uint64_t> offsets(n + 1), out_offsets(m + 1);
         std::vector<ck_windows::Window> windows(m ? m : 1);
-        Block payload(h[4], lead + nb, IN_CANARY);
-        if (!get(in, offsets.data(), 8 * (n + 1)) || !get(in, payload.use() + lead, nb) || !get(in, windows.data(), sizeof(ck_windows::Window) * m)) {
+        ck_emu::LeadBlock payload(h[4], lead, nb, IN_CANARY);
+        if (!get(in, offsets.data(), 8 * (n + 1)) || !get(in, payload.payload(), nb) || !get(in, windows.data(), sizeof(ck_windows::Window) * m)) {
             fprintf(stderr, "case %llu: short body\n", (unsigned long long)c);
             return 2;
         }
         for (uint64_t& o : offsets) o += lead;
-        std::vector<uint8_t> before(payload.use(), payload.use() + lead + nb);
+        payload.keep();
         const std::vector<ck_windows::Window> windows_before = windows;
 
         uint64_t n_invalid = 0, total = 0;
@@ -142,7 +144,7 @@ int main(int argc, char** argv)
             }
         }
         const uint64_t written = refused ? 0 : total;
-        if (!payload.intact(lead + nb) || memcmp(before.data(), payload.use(), lead + nb) || !output.intact(written) ||
+        if (!payload.unchanged() || !output.intact(written) ||
             memcmp(windows_before.data(), windows.data(), sizeof(ck_windows::Window) * m))
             rc = rc ? rc : RC_CANARY;
         const uint64_t r[4] = { rc, total, n_invalid, refused };

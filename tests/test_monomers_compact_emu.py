@@ -83,3 +83,16 @@ def test_decide_on_random_triples_equals_the_plain_restatement():
                 dict(min_overlap_percent=1.0, keep_all=True), dict(min_length=3, min_overlap=2, min_overlap_percent=0.25, max_length=38)):
         exp = check(("random", data, offs, ends, full, flt))
         MR.assert_equal(exp, MR.compact_slow(data, offs, ends, full, **flt), flt)
+
+
+def test_a_payload_across_byte_2_32():
+    """The payload 2^32 bytes, less half a record, into a lazily reserved buffer (tests/high_base.py, "middle"): the longest record
+    straddles byte 2^32 of the buffer, the records behind it lie wholly above, and payload positions need 33 bits."""
+    from tests import high_base as H
+    ran = 0
+    for s in (MS.misalignment_set(), MS.emulator_sets(E.tile_bytes())[0], MS.emulator_sets(E.tile_bytes())[13]):
+        j = H.inner_longest(s[2])
+        absolute = H.conditions(s[1], s[2], j, "middle")
+        check(s, in_shift=5, out_shift=11, lead=int(absolute[0]))
+        ran += 1
+    assert ran == 3 and MS.emulator_sets(E.tile_bytes())[13][0] == "a monomer across tiles"

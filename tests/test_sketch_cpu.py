@@ -226,3 +226,17 @@ def test_compare_as_fibers(tmp_path):
         m, f, n_bad = R.compare_pairs(a, a if other is None else other, pairs)
         assert bad == n_bad and np.array_equal(match, m) and np.array_equal(filled, f)
         assert not pairs or (bad >= 3 and match.max() == a.shape[1])
+
+
+def test_a_payload_across_byte_2_32_as_fibers(tmp_path):
+    """Every length of the set, and one record of three spans and a tail in their middle, with the payload 2^32 bytes, less half
+    that record, into a lazily reserved buffer (tests/high_base.py, "middle"): byte 2^32 of the buffer lies inside the record's second
+    span, half of the short records lie wholly above it, and payload positions need 33 bits."""
+    from tests import high_base as H
+    from tests.emu import sketch_emu
+    recs, j, seg = H.sketch_records("lengths", 21)
+    data, offs = S.pack(recs)
+    lead = int(H.conditions(data, offs, j, "middle")[0])
+    got = sketch_emu.run_sketch([(data, offs, dict(k=21, log2_bins=8, seed=3), dict(lead=lead, in_shift=7, long_grid=4))], tmp_path)[0]
+    check(got, recs, 21, 8, 3, "across 2^32")
+    assert got[4] >= 4                                                          # (the records of more than one span)

@@ -189,3 +189,19 @@ def test_fibers_refuse_a_short_capacity(tmp_path):
     for out, out_off, total, _ in got[:2]:
         assert out is None and total == len(exp) and np.array_equal(out_off, exp_off)      # (the program found every byte still canary)
     assert np.array_equal(got[2][0], exp)
+
+
+def test_a_payload_across_byte_2_32_as_fibers(tmp_path):
+    """The grid case and the window across tiles with the payload 2^32 bytes, less half a record, into a lazily reserved buffer
+    (tests/high_base.py, "middle"): the 100-symbol record straddles byte 2^32 of the buffer, the 1000-symbol record lies wholly above
+    it, and payload positions need 33 bits."""
+    from tests import high_base as H
+    from tests.emu import windows_emu
+    cases = [S.all_cases()[0], S.all_cases()[-1]]
+    assert cases[1][0] == "a window across tiles"
+    leads = [int(H.conditions(data, offs, H.inner_longest(offs), "middle")[0]) for _, data, offs, _, _ in cases]
+    got = windows_emu.run([(d, o, w, dict(p, lead=lead)) for (_, d, o, w, p), lead in zip(cases, leads)], tmp_path)
+    for (name, data, offs, wins, _), (out, out_off, total, bad) in zip(cases, got):
+        exp, exp_off, exp_bad = R.gather(data, offs, wins)
+        assert np.array_equal(out_off, exp_off) and total == len(exp) and bad == exp_bad, name
+        assert np.array_equal(out, exp), name
