@@ -9,7 +9,7 @@ cluster.py  text -> sketch -> candidates -> compare -> link -> representatives a
 prealign.py  the same chain, then every record rotated and flipped onto its cluster's representative (also
            `python -m circkit_amd.prealign`)
 """
-from .api import (ANCHOR_NONE, GENETIC_CODES, SKETCH_EMPTY, CirckitError, Context, canonicalize, cat_batch, cluster_batch, cluster_params, decat_batch, default_context, fasta_parse_gpu, fasta_write_gpu, find_orfs,  # noqa: F401
+from .api import (ANCHOR_NONE, DISTANCE_MAX, DISTANCE_OVER, GENETIC_CODES, SKETCH_EMPTY, CirckitError, Context, canonicalize, cat_batch, cluster_batch, cluster_params, decat_batch, default_context, distance_params, edit_distances, fasta_parse_gpu, fasta_write_gpu, find_orfs,  # noqa: F401
                   lmsr,
                   lmsr_index, load_library, monomer_end_index, monomer_filter, monomerize_params, monomers_batch, normalize, orf_params,
                   orf_proteins, orf_sequences, prealign_batch, prealign_params, revcomp_batch, rotate_batch, sketch_anchors, sketch_batch, sketch_params, sketch_similarity, translate_params, uniq_batch, windows_translate, xxh3_64)

@@ -113,6 +113,9 @@ SIGNATURES = {
     "circkit_prealign_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 2),
     "circkit_prealign_pairs_of_labels_device": (_i, [_vp, _vp, _u64, _vp]),
     "circkit_prealign_batch": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "circkit_distance_pairs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "circkit_distance_status": (_i, [_vp] + [ctypes.POINTER(_u64)] * 2),
+    "circkit_distance_pairs": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "circkit_version": (ctypes.c_char_p, []),
 }
 
@@ -197,6 +200,23 @@ def prealign_params(k=21, log2_bins=8, min_votes=4):
     aligned when at least min_votes (>= 1) shared bins agree on one rotation and strand.  The library checks the ranges."""
     p = PrealignParams()
     p.k, p.log2_bins, p.min_votes = int(k), int(log2_bins), int(min_votes)
+    return p
+
+
+# circkit_distance_params / CIRCKIT_DISTANCE_OVER / CIRCKIT_DISTANCE_MAX (include/circkit.h)
+DISTANCE_OVER = 0xFFFFFFFF
+DISTANCE_MAX = 255
+
+
+class DistanceParams(ctypes.Structure):
+    _fields_ = [("max_distance", _u32), ("reserved", _u32 * 3)]
+
+
+def distance_params(max_distance=32):
+    """circkit_distance_params from Python values: a pair's distance is reported when it is at most max_distance (0 .. 255) and
+    as DISTANCE_OVER otherwise.  The library checks the range."""
+    p = DistanceParams()
+    p.max_distance = int(max_distance) & 0xFFFFFFFF
     return p
 
 
@@ -923,6 +943,43 @@ class Context:
                                                      _ptr(scores) if m else None))
         return windows, scores
 
+    # -- edit distance of record pairs ---------------------------------------------------------------
+    def distance_pairs_device(self, d_bytes_a, d_offsets_a, n_a, d_bytes_b, d_offsets_b, n_b, d_pairs, n_pairs, d_out_distance=None,
+                              d_out_scores=None, params=None, **kw):
+        """Enqueues circkit_distance_pairs_device: d_out_distance[p] (uint32, device, optional) = the edit distance of record
+        d_pairs[2p] of batch A and record d_pairs[2p + 1] of batch B when it is at most max_distance, DISTANCE_OVER otherwise;
+        d_out_scores[2p], d_out_scores[2p + 1] (optional) = (L - distance, L) with L the longer record's length, what
+        cluster_link_device takes.  params: a distance_params() result, or its keywords.  distance_status() waits."""
+        p = params if params is not None else distance_params(**kw)
+        self._check(self._lib.circkit_distance_pairs_device(self._h, _ptr(d_bytes_a), _ptr(d_offsets_a), int(n_a), _ptr(d_bytes_b), _ptr(d_offsets_b),
+                                                            int(n_b), ctypes.byref(p), _ptr(d_pairs), int(n_pairs), _ptr(d_out_distance),
+                                                            _ptr(d_out_scores)))
+
+    def distance_status(self):
+        """Waits for the last distance pairs call; returns (pairs within max_distance, invalid pairs).  Raises CirckitError
+        (INVALID_ARG) when a pair named a record that does not exist or has 2^31 symbols or more."""
+        a, bad = _u64(0), _u64(0)
+        self._check(self._lib.circkit_distance_status(self._h, ctypes.byref(a), ctypes.byref(bad)))
+        return a.value, bad.value
+
+    def distance_pairs(self, data_a, offsets_a, data_b, offsets_b, pairs, max_distance=32):
+        """(distance, scores) of the pairs (i, j) of two host CSR batches: a uint32 array with DISTANCE_OVER where the distance
+        exceeds max_distance, and an (n_pairs, 2) uint32 array of (L - distance, L).  data_b = offsets_b = None: one batch."""
+        data_a = np.ascontiguousarray(data_a, dtype=np.uint8)
+        offsets_a = np.ascontiguousarray(offsets_a, dtype=np.uint64)
+        same = data_b is None and offsets_b is None
+        data_b = data_a if same else np.ascontiguousarray(data_b, dtype=np.uint8)
+        offsets_b = offsets_a if same else np.ascontiguousarray(offsets_b, dtype=np.uint64)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        p = distance_params(max_distance=max_distance)
+        m = len(pairs)
+        dist = np.zeros(m, dtype=np.uint32)
+        scores = np.zeros((m, 2), dtype=np.uint32)
+        self._check(self._lib.circkit_distance_pairs(self._h, _ptr(data_a) if len(data_a) else None, _ptr(offsets_a), len(offsets_a) - 1,
+                                                     _ptr(data_b) if len(data_b) else None, _ptr(offsets_b), len(offsets_b) - 1, ctypes.byref(p),
+                                                     _ptr(pairs) if m else None, m, _ptr(dist) if m else None, _ptr(scores) if m else None))
+        return dist, scores
+
     def _records_windows(self, data, offsets, kind, bases=0, percent=0.0):
         """One copy in, the windows of `kind` and their gather on the device, one copy home: (bytes, offsets)."""
         import torch
@@ -1304,6 +1361,14 @@ def prealign_batch(seqs, pairs, k=21, log2_bins=8, seed=0, min_votes=4):
     fewer than min_votes agreeing bins gets the identity window."""
     data, offsets = _csr_of(seqs)
     return default_context().prealign_batch(data, offsets, pairs, k=k, log2_bins=log2_bins, seed=seed, min_votes=min_votes)
+
+
+def edit_distances(seqs_a, seqs_b, pairs, max_distance=32):
+    """The edit distance of record i of seqs_a and record j of seqs_b (seqs_b = None: of seqs_a too) for every pair (i, j): a
+    uint32 array, DISTANCE_OVER where the distance exceeds max_distance (0 .. 255).  Symbols are bytes as they are."""
+    data_a, offsets_a = _csr_of(seqs_a)
+    data_b, offsets_b = (None, None) if seqs_b is None else _csr_of(seqs_b)
+    return default_context().distance_pairs(data_a, offsets_a, data_b, offsets_b, pairs, max_distance=max_distance)[0]
 
 
 def orf_proteins(data, offsets, include_stop=False, **kw):

@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcirckit_hip.so")
 CLI = os.path.join(HERE, "circkit")
 HIP_SOURCES = ["circkit_hip.hip", "circkit_canon.hip", "circkit_bench.hip", "circkit_uniq.hip", "circkit_uniq_compact.hip", "circkit_orfs.hip", "circkit_monomerize.hip", "circkit_windows.hip",
-               "circkit_fasta.hip", "circkit_fasta_write.hip", "circkit_sketch.hip", "circkit_cluster.hip", "circkit_prealign.hip", "fasta_host.cpp"]
+               "circkit_fasta.hip", "circkit_fasta_write.hip", "circkit_sketch.hip", "circkit_cluster.hip", "circkit_prealign.hip", "circkit_distance.hip", "fasta_host.cpp"]
 HOST_SOURCES = ["circkit_cli.cpp"]
 
 

@@ -29,7 +29,7 @@ inline int ck_ctx_fail(circkit_ctx* c, int code, const char* msg) { return ck_fa
 
 // One slot of state per unit: *slot is null until the unit puts its state there; circkit_ctx_destroy hands whatever it
 // finds to the `release` the unit named.
-enum ck_unit { CK_UNIT_ORFS, CK_UNIT_MONOMERIZE, CK_UNIT_UNIQ, CK_UNIT_UNIQ_COMPACT, CK_UNIT_WINDOWS, CK_UNIT_FASTA, CK_UNIT_FASTA_WRITE, CK_UNIT_SKETCH, CK_UNIT_CLUSTER, CK_UNIT_PREALIGN, CK_N_UNITS };
+enum ck_unit { CK_UNIT_ORFS, CK_UNIT_MONOMERIZE, CK_UNIT_UNIQ, CK_UNIT_UNIQ_COMPACT, CK_UNIT_WINDOWS, CK_UNIT_FASTA, CK_UNIT_FASTA_WRITE, CK_UNIT_SKETCH, CK_UNIT_CLUSTER, CK_UNIT_PREALIGN, CK_UNIT_DISTANCE, CK_N_UNITS };
 void** ck_ctx_slot(circkit_ctx* c, ck_unit unit, void (*release)(void*));
 
 // The uniq unit's overflow word on the device (circkit_uniq.hip): the records whose key found no slot since the table was last

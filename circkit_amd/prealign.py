@@ -10,7 +10,9 @@ circkit_amd/cluster.py does (candidates, compare, link), every record paired wit
 (circkit_prealign_pairs_device); circkit_windows_gather_device cuts all n records, in input order, and circkit_fasta_write_device
 writes each under its own head.  Representatives and records that did not reach min_votes come out as they went in.  The table
 holds `record<TAB>representative<TAB>strand<TAB>start<TAB>votes<TAB>matches` for every record, the first word of either head,
-under a title row of those six words.
+under a title row of those six words.  With max_distance = W (`--max-distance W`) the table has a seventh column `distance`:
+the bounded edit distance of the record as it comes out and its representative (circkit_distance_pairs_device on the gathered
+batch), or `*` when it is more than W.
 """
 import argparse
 import sys
@@ -27,9 +29,11 @@ def _word(head):
     return parts[0] if parts else b""
 
 
-def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min_similarity=0.2, min_filled=8, min_votes=4, ctx=None):
+def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min_similarity=0.2, min_filled=8, min_votes=4, max_distance=None,
+                   ctx=None):
     """The whole chain on FASTA text: (every record rotated onto its representative as FASTA, the table, the labels as a uint64
-    array).  Raises ValueError on a FASTA format error, CirckitError on parameters out of range."""
+    array).  Raises ValueError on a FASTA format error, CirckitError on parameters out of range.  max_distance: the table's seventh
+    column, see above."""
     import torch
     text = bytes(text)
     ctx = ctx or api.default_context()
@@ -37,8 +41,11 @@ def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min
     sp = api.sketch_params(k=k, log2_bins=log2_bins, seed=seed)
     pp = api.prealign_params(k=k, log2_bins=log2_bins, min_votes=min_votes)
     n_text = len(text)
+    title = TITLE if max_distance is None else TITLE[:-1] + b"\tdistance\n"
+    if max_distance is not None:
+        dp = api.distance_params(max_distance=max_distance)
     if n_text == 0:
-        return b"", TITLE, np.zeros(0, dtype=np.uint64)
+        return b"", title, np.zeros(0, dtype=np.uint64)
     dev = torch.device("cuda", ctx.device)
     cap_r = (n_text + 1) // 2
     with torch.cuda.device(dev):
@@ -55,7 +62,7 @@ def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min
                 raise ValueError(str(e))
             raise
         if n == 0:
-            return b"", TITLE, np.zeros(0, dtype=np.uint64)
+            return b"", title, np.zeros(0, dtype=np.uint64)
         d_rows = torch.empty(n << sp.log2_bins, dtype=torch.int64, device=dev)
         d_anchors = torch.empty(n << sp.log2_bins, dtype=torch.int32, device=dev)
         capacity = n * p.n_bands
@@ -77,11 +84,17 @@ def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min
         ctx.prealign_pairs_of_labels_device(d_labels, n, d_rep_pairs)
         ctx.prealign_pairs_device(d_rows, d_anchors, d_offs, n, d_rep_pairs, n, d_win, d_votes, params=pp)
         ctx.windows_gather_device(d_data, d_offs, n, d_win, n, d_cut, n_bytes, d_cut_off)
+        if max_distance is not None:                            # a representative's own window is the identity: the cut batch holds both sides
+            d_dist = torch.empty(n, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream().synchronize()
+            ctx.distance_pairs_device(d_cut, d_cut_off, n, d_cut, d_cut_off, n, d_rep_pairs, n, d_dist, None, params=dp)
         ctx.sketch_status()
         ctx.sketch_compare_status()
         ctx.cluster_link_status()
         ctx.prealign_status()
         cut_bytes, _ = ctx.windows_status()
+        if max_distance is not None:
+            ctx.distance_status()
         assert cut_bytes == n_bytes                             # every window is as long as its record
         cap = n_text + cut_bytes + 2 * n + 16                  # every head lies in the text
         d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -94,9 +107,11 @@ def prealign_fasta(text, k=21, log2_bins=8, seed=0, n_bands=64, band_bins=2, min
         win = d_win.cpu().numpy().view(api.WINDOW_DTYPE)
         votes = d_votes.cpu().numpy().view(np.uint32).reshape(n, 2)
         head = d_spans[0, :n].cpu().numpy().view(np.uint64)
+        dist = None if max_distance is None else d_dist.cpu().numpy().view(np.uint32)
     words = [_word(text[int(h[0]):int(h[0] + h[1])]) for h in head]
-    table = TITLE + b"".join(b"%s\t%s\t%d\t%d\t%d\t%d\n" % (words[i], words[int(labels[i])], win["strand"][i], win["start"][i], votes[i][0], votes[i][1])
-                             for i in range(n))
+    last = [b""] * n if dist is None else [b"\t*" if d == api.DISTANCE_OVER else b"\t%d" % d for d in dist]
+    table = title + b"".join(b"%s\t%s\t%d\t%d\t%d\t%d%s\n" % (words[i], words[int(labels[i])], win["strand"][i], win["start"][i], votes[i][0], votes[i][1],
+                                                               last[i]) for i in range(n))
     return fasta, table, labels
 
 
@@ -114,6 +129,8 @@ def _parser():
     p.add_argument("--band-bins", type=int, default=2, help="bins of a band, 1 .. 16")
     p.add_argument("--min-similarity", type=float, default=0.2, help="a pair links at match / filled of at least this")
     p.add_argument("--min-votes", type=int, default=4, help="a record is rotated when this many shared bins agree on one rotation and strand")
+    p.add_argument("--max-distance", type=int, default=None,
+                   help="add a column `distance` to the table: the edit distance of each record as written and its representative, 0 .. 255, `*` beyond")
     p.add_argument("--table", help="record, representative, strand, start, votes, matches for every record, tab separated")
     return p
 
@@ -134,7 +151,7 @@ def main(argv=None):
         return 1
     try:
         fasta, table, _ = prealign_fasta(text, k=a.k, log2_bins=a.bins.bit_length() - 1, n_bands=a.bands, band_bins=a.band_bins,
-                                         min_similarity=a.min_similarity, min_votes=a.min_votes)
+                                         min_similarity=a.min_similarity, min_votes=a.min_votes, max_distance=a.max_distance)
     except (ValueError, api.CirckitError) as e:
         sys.stderr.write("Error: %s\n" % e)
         return 1

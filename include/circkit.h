@@ -682,6 +682,50 @@ int circkit_prealign_batch(circkit_ctx* ctx, const uint8_t* bytes, const uint64_
                            const circkit_sketch_params* sketch, const uint32_t* pairs, uint64_t n_pairs, uint32_t min_votes,
                            circkit_window* windows, uint32_t* scores);
 
+/* ---- edit distance of record pairs --------------------------------------------------------------- */
+/* Nothing in the reference is replaced: this is the first linear tool behind `prealign`, which puts two records into one frame.
+ * BATCHES AND PAIRS.  Two CSR batches, A (d_bytes_a, d_offsets_a, n_a records) and B (likewise); they may be the same pointers.
+ * offsets[0] need not be 0 and the payloads need no alignment.  Pair p = (i, j) = d_pairs[2p], d_pairs[2p + 1], in the compare's
+ * layout: i indexes A, j indexes B; x = A[i] with n_x symbols, y = B[j] with n_y symbols.
+ * SYMBOLS are bytes, equal iff their bytes are equal: N equals N, a differs from A, there is no wildcard, 0x00 and 0xFF are legal.
+ * RESULT.  lev(x, y) is the Levenshtein distance with unit costs for substitution, insertion and deletion.  With
+ * W = params.max_distance: distance = lev(x, y) if lev(x, y) <= W, CIRCKIT_DISTANCE_OVER otherwise.  This depends on no band
+ * geometry: any correct bounded algorithm gives the same bits.  Part of the contract: |n_x - n_y| > W gives OVER and no byte of
+ * either record is read; an empty record against one of n <= W symbols gives n; a pair (i, i) on one batch gives 0.  A pair with
+ * i >= n_a or j >= n_b, or in which either record has 2^31 symbols or more, is INVALID: distance OVER, scores (0, 0), counted, and
+ * nothing it names is read.
+ * SCORES.  For a valid pair, with L = max(n_x, n_y): (L - distance, L) when the distance is within W, (0, L) when OVER.  This is
+ * the (match, filled) layout circkit_cluster_link_device takes: a pair links iff filled >= min_filled and
+ * ((L - d) << 16) >= min_similarity_q16 * L, that is identity 1 - d / L of at least the threshold, and d <= W. */
+typedef struct circkit_distance_params {
+    uint32_t max_distance;                   /* W: 0 .. CIRCKIT_DISTANCE_MAX */
+    uint32_t reserved[3];                    /* 0 */
+} circkit_distance_params;
+#define CIRCKIT_DISTANCE_MAX 255u
+#define CIRCKIT_DISTANCE_OVER 0xFFFFFFFFu
+
+/* The distance and scores of every pair (no counterpart in the reference).  Device pointers; the call only enqueues on the ctx
+ * stream.  d_offsets_a / d_offsets_b: uint64[n + 1], 8-byte aligned; d_pairs: uint32[2 * n_pairs]; d_out_distance:
+ * uint32[n_pairs], nullable; d_out_scores: uint32[2 * n_pairs], nullable; all 4-byte aligned.  Both outputs null with pairs,
+ * max_distance out of range, reserved != 0, null inputs with work, n_a or n_b >= 2^32, or an output overlapping the offsets, the
+ * pairs or the other output: INVALID_ARG, nothing enqueued, buffers and earlier totals unchanged.  Keeping the outputs off the
+ * payloads is the caller's contract, as in the sketch unit.  n_pairs == 0 is valid.  Bit-identical from run to run. */
+int circkit_distance_pairs_device(circkit_ctx* ctx, const uint8_t* d_bytes_a, const uint64_t* d_offsets_a, uint64_t n_a,
+                                  const uint8_t* d_bytes_b, const uint64_t* d_offsets_b, uint64_t n_b,
+                                  const circkit_distance_params* params, const uint32_t* d_pairs, uint64_t n_pairs,
+                                  uint32_t* d_out_distance, uint32_t* d_out_scores);
+/* Waits for the most recent pairs call of this ctx (device or host form): *n_within = its pairs with a distance of at most W,
+ * *n_invalid = its invalid pairs; CIRCKIT_ERR_INVALID_ARG when there was any, after the valid pairs were written.  The totals are
+ * the call's own, whatever other unit ran in between. */
+int circkit_distance_status(circkit_ctx* ctx, uint64_t* n_within, uint64_t* n_invalid);
+/* The same with HOST buffers on one stream: copy in (once when A and B are the same pointers), the pairs call, copy the outputs
+ * that are not null home, synchronize.  offsets[0] must be 0 and the offsets must not decrease; a record of 2^31 symbols or more
+ * is refused from the offsets alone: CIRCKIT_ERR_TOO_LONG, nothing computed.  Invalid pairs: CIRCKIT_ERR_INVALID_ARG after the
+ * valid ones were written.  The staging is the ctx's and only grows. */
+int circkit_distance_pairs(circkit_ctx* ctx, const uint8_t* bytes_a, const uint64_t* offsets_a, uint64_t n_a,
+                           const uint8_t* bytes_b, const uint64_t* offsets_b, uint64_t n_b, const circkit_distance_params* params,
+                           const uint32_t* pairs, uint64_t n_pairs, uint32_t* out_distance, uint32_t* out_scores);
+
 /* ---- FASTA -> CSR packer (host logic, no GPU) --------------------------------------------------- */
 /* Replaces seq_io 0.3.2's fasta::Reader record boundaries + the normalize step of the worker closure
  * (src/canonicalize.rs:14-27, src/uniq.rs:24-38).  Parses the complete records of text[0, n): header span,
