@@ -34,15 +34,6 @@ int ensure_lists(circkit_ctx* c, uint64_t entries, uint64_t segs)
     return CIRCKIT_OK;
 }
 
-int ensure_gscratch(circkit_ctx* c, uint64_t bytes)
-{
-    if (bytes <= c->cap_gscratch) return CIRCKIT_OK;
-    if (c->d_gscratch) { (void)hipFree(c->d_gscratch); c->d_gscratch = nullptr; c->cap_gscratch = 0; }
-    CK_HIP(c, hipMalloc(&c->d_gscratch, bytes));
-    c->cap_gscratch = bytes;
-    return CIRCKIT_OK;
-}
-
 // What one stage of a batch hands to the next: the kernel arguments as the stage before left them, and the segments and the
 // capacity of the list the next stage consumes.  The rest is fixed for the batch.
 struct Batch {
@@ -254,7 +245,7 @@ void stage_global(circkit_ctx* c, Batch& b)
     ck::CanonArgs& a = b.a;
     const unsigned nseg = b.nseg;
     const uint32_t seg_cap = b.seg_cap;
-    const uint64_t cap_dw = c->cap_gscratch / 4;
+    const uint64_t cap_dw = c->d_gscratch.cap / 4;
     const uint64_t slice1 = cap_dw < GSLICE1_DW ? cap_dw : GSLICE1_DW;
     const unsigned max_w1 = (unsigned)(cap_dw / slice1 < 64 ? cap_dw / slice1 : 64);
     const unsigned spb1 = (nseg + max_w1 - 1) / max_w1, w1 = (nseg + spb1 - 1) / spb1;
@@ -267,7 +258,7 @@ void stage_global(circkit_ctx* c, Batch& b)
     a2.in_nseg = w1; a2.in_seg_cap = spb1 * seg_cap; a2.segs_per_block = w1;
     a2.defer_list = nullptr; a2.defer_count = nullptr; a2.out_seg_cap = 0;
     a2.slice_dw = (uint32_t)(cap_dw < 0xFFFFFFFFull ? cap_dw : 0xFFFFFFFFull);
-    hipLaunchKernelGGL(canon_global_kernel, dim3(w1), dim3(TEAM_WAVES * 64), 0, c->stream, a, a2, c->d_gscratch, c->d_counters + 2, (const uint32_t*)c->d_counters,
+    hipLaunchKernelGGL(canon_global_kernel, dim3(w1), dim3(TEAM_WAVES * 64), 0, c->stream, a, a2, (uint32_t*)c->d_gscratch.p, c->d_counters + 2, (const uint32_t*)c->d_counters,
                        (const uint32_t*)(c->d_counters + 1), c->d_mode + 1);
 }
 
@@ -315,25 +306,17 @@ int launch_canon(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offse
     // + 1024 segments of slack: a stage that merges k segments per workgroup addresses up to k - 1 segments past the end
     int rc = ensure_lists(c, (uint64_t)g.G * g.cap + 1024ull * g.cap, g.G < 256u ? 256u : g.G);
     if (rc) return rc;
-    if (!c->d_gscratch && (rc = ensure_gscratch(c, c->gscratch_default))) return rc;
+    if (!c->d_gscratch && (rc = c->d_gscratch.grow(c, c->gscratch_default))) return rc;
     uint32_t* view = nullptr;
     if (d_hash && !d_out) {
         // hash-only (uniq without --canonicalize, src/uniq.rs:55-60): no canonical bytes are written anywhere.  A record
         // whose hash is not fused leaves its canonical form as a view of the input -- strand + rotation, one u32 in a ctx
         // array sized by n (known here: no look at the device, no synchronisation) -- and the xxh3 pass hashes that view.
-        if (n > c->cap_view) {
-            if (c->d_view) { (void)hipFree(c->d_view); c->d_view = nullptr; c->cap_view = 0; }
-            CK_HIP(c, hipMalloc(&c->d_view, (n + n / 8 + 64) * sizeof(uint32_t)));
-            c->cap_view = n + n / 8 + 64;
-        }
+        if (n > c->d_view.cap && (rc = c->d_view.grow(c, n + n / 8 + 64))) return rc;
         view = c->d_view;
     }
     if (d_hash) {
-        if (n > c->cap_hashed) {
-            if (c->d_hashed) { (void)hipFree(c->d_hashed); c->d_hashed = nullptr; c->cap_hashed = 0; }
-            CK_HIP(c, hipMalloc(&c->d_hashed, n + n / 8 + 64));
-            c->cap_hashed = n + n / 8 + 64;
-        }
+        if (n > c->d_hashed.cap && (rc = c->d_hashed.grow(c, n + n / 8 + 64))) return rc;
         CK_HIP(c, hipMemsetAsync(c->d_hashed, 0, n, c->stream));
     }
     // d_counters: [0] records the last LDS tier passed on, [2] arrival ticket of the global-scratch kernel (leaves it zero),
@@ -384,10 +367,10 @@ int launch_single(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs
         a.slice_dw = TIER_DW[t];
         hipLaunchKernelGGL(canon_kernel<1>, dim3(1), dim3(64), (TIER_DW[t] + TIER_EXTRA_DW) * 4, c->stream, a, 1u, (uint32_t*)nullptr);
     } else {
-        int rc = ensure_gscratch(c, need * 4);
+        int rc = c->d_gscratch.grow(c, need * 4);
         if (rc) return rc;
         a.slice_dw = (uint32_t)(need < 0xFFFFFFFFull ? need : 0xFFFFFFFFull);
-        hipLaunchKernelGGL(canon_global_one_kernel, dim3(1), dim3(64), 0, c->stream, a, c->d_gscratch);
+        hipLaunchKernelGGL(canon_global_one_kernel, dim3(1), dim3(64), 0, c->stream, a, (uint32_t*)c->d_gscratch.p);
     }
     if (d_hash) hipLaunchKernelGGL(xxh3_kernel, dim3(1), dim3(256), 0, c->stream, d_out, d_offsets, (uint64_t)1, d_hash, (const uint8_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr);
     CK_HIP(c, hipGetLastError());
@@ -493,7 +476,7 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     // launch_canon allocates the default only when there is none -- and a later device batch would find its long records refused)
     if (worst_case_dw(max_len) > TIER_D_DW) {
         const uint64_t want = worst_case_dw(max_len) * 4;
-        if ((rc = ensure_gscratch(c, want < c->gscratch_default ? c->gscratch_default : want))) return rc;
+        if ((rc = c->d_gscratch.grow(c, want < c->gscratch_default ? c->gscratch_default : want))) return rc;
     }
     // The batch goes through the device in PARTS of >= 16 MB (up to sixteen): part k + 1 is copied in while part k - 1 is copied
     // out on a stream of the ctx's own; with page-locked buffers (circkit_host_alloc) the two directions of the link work at
@@ -659,7 +642,7 @@ int circkit_ctx_batch_status(circkit_ctx* c, uint32_t* n_unprocessed)
     CK_HIP(c, hipStreamSynchronize(c->stream));
     if (*n_unprocessed)
         return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "%u record(s) were not processed: longer than the long-record scratch (%llu MiB, "
-                    "circkit_ctx_set_long_record_scratch) or than 2^31 symbols", *n_unprocessed, (unsigned long long)(c->cap_gscratch >> 20));
+                    "circkit_ctx_set_long_record_scratch) or than 2^31 symbols", *n_unprocessed, (unsigned long long)(c->d_gscratch.cap >> 20));
     return CIRCKIT_OK;
 }
 
@@ -670,7 +653,7 @@ int circkit_ctx_set_long_record_scratch(circkit_ctx* c, uint64_t bytes)
     if (bytes < (1ull << 20)) bytes = 1ull << 20;
     c->gscratch_default = bytes;
     CK_HIP(c, hipStreamSynchronize(c->stream));        // a batch in flight may be using the old one
-    return ensure_gscratch(c, bytes);
+    return c->d_gscratch.grow(c, bytes);
 }
 
 int circkit_ctx_last_batch_mode(circkit_ctx* c, uint32_t* mode)

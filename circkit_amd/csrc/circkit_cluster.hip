@@ -18,6 +18,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "ck_scan.h"
 #include "cluster.h"
@@ -100,54 +101,21 @@ struct ClusterState {
     ck_totals link;                  // [L_WORDS], of the most recent link
     bool any_cand = false, any_link = false;
     uint64_t capacity = 0;           // of the most recent candidates call
-    uint64_t* d_keys = nullptr; uint64_t cap_keys = 0;          // n_records * n_bands (grow only, as everything below)
-    uint64_t* d_first = nullptr; uint64_t cap_first = 0;
-    uint64_t* d_masks = nullptr; uint64_t cap_masks = 0;
-    uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
-    uint32_t* d_parent = nullptr; uint64_t cap_parent = 0;
+    ck_buf<uint64_t> d_keys, d_first;        // n_records * n_bands
+    ck_buf<uint64_t> d_masks, d_sums;
+    ck_buf<uint32_t> d_parent;
     // the staging of circkit_cluster_batch
-    uint8_t* d_bytes = nullptr; uint64_t cap_bytes = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    uint64_t* d_rows = nullptr; uint64_t cap_rows = 0;
-    uint64_t* d_pair_off = nullptr; uint64_t cap_pair_off = 0;
-    uint32_t* d_pairs = nullptr; uint64_t cap_pairs = 0;
-    uint32_t* d_scores = nullptr; uint64_t cap_scores = 0;
-    uint64_t* d_labels = nullptr; uint64_t cap_labels = 0;
+    ck_csr_buf in;
+    ck_buf<uint64_t> d_rows, d_pair_off, d_labels;
+    ck_buf<uint32_t> d_pairs, d_scores;
 };
-
-void release_state(void* p)
-{
-    ClusterState* S = (ClusterState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_keys, S->d_first, S->d_masks, S->d_sums, S->d_parent, S->d_bytes, S->d_off, S->d_rows, S->d_pair_off, S->d_pairs,
-                     S->d_scores, S->d_labels };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->cand);
-    ck_totals_release(&S->link);
-    delete S;
-}
 
 int state(circkit_ctx* c, ClusterState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_CLUSTER, release_state);
-    if (!*slot) *slot = new ClusterState();
-    ClusterState* S = (ClusterState*)*slot;
-    *out = S;
+    ClusterState* S = *out = ck_unit_state<ClusterState>(c, CK_UNIT_CLUSTER);
     int rc;
     if ((rc = ck_totals_make(c, &S->cand, C_WORDS))) return rc;
     return ck_totals_make(c, &S->link, L_WORDS);
-}
-
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-uint32_t grid_of(uint64_t work, uint32_t per_block, uint32_t max_grid)
-{
-    const uint64_t blocks = (work + per_block - 1) / per_block;
-    return (uint32_t)(blocks > max_grid ? max_grid : blocks);
 }
 
 int check_params(circkit_ctx* c, const circkit_cluster_params* p)
@@ -178,10 +146,10 @@ int launch_candidates(circkit_ctx* c, ClusterState* S, const uint64_t* d_sketch,
 {
     const uint64_t n_keys = n * p.n_bands, tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     int rc;
-    if ((rc = ck_grow(c, &S->d_keys, &S->cap_keys, n_keys ? n_keys : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_first, &S->cap_first, n_keys ? n_keys : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_masks, &S->cap_masks, n ? n : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = S->d_keys.grow(c, n_keys))) return rc;
+    if ((rc = S->d_first.grow(c, n_keys))) return rc;
+    if ((rc = S->d_masks.grow(c, n))) return rc;
+    if ((rc = S->d_sums.grow(c, tiles))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if ((rc = ck_totals_clear(c, &S->cand, C_WORDS))) return rc;
     Emit E;
@@ -190,20 +158,20 @@ int launch_candidates(circkit_ctx* c, ClusterState* S, const uint64_t* d_sketch,
     if (n) {
         Keys K;
         K.rows = d_sketch; K.n_records = n; K.log2_bins = log2_bins; K.n_bands = p.n_bands; K.band_bins = p.band_bins; K.keys = S->d_keys;
-        hipLaunchKernelGGL(cluster_keys_kernel, dim3(grid_of(n_keys, KEYS_WG, KEYS_MAX_GRID)), dim3(KEYS_WG), 0, st, K);
+        hipLaunchKernelGGL(cluster_keys_kernel, dim3(ck_grid_of(n_keys, KEYS_WG, KEYS_MAX_GRID)), dim3(KEYS_WG), 0, st, K);
         CK_HIP(c, hipGetLastError());
         if ((rc = circkit_uniq_resolve_device(c, S->d_keys, n_keys, 0, S->d_first, nullptr))) return rc;
         // the resolve's overflow count while it is still this call's: the table is anybody's after the next circkit_uniq_reset
         const uint32_t* d_overflow;
         if ((rc = ck_uniq_overflow_word(c, &d_overflow))) return rc;
         CK_HIP(c, hipMemcpyAsync(S->cand.d + ck_cluster::C_OVERFLOW, d_overflow, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(cluster_count_kernel, dim3(grid_of(n, EMIT_WAVES, EMIT_MAX_GRID)), dim3(64 * EMIT_WAVES), 0, st, E);
+        hipLaunchKernelGGL(cluster_count_kernel, dim3(ck_grid_of(n, EMIT_WAVES, EMIT_MAX_GRID)), dim3(64 * EMIT_WAVES), 0, st, E);
         hipLaunchKernelGGL(cluster_tile_sums_kernel, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_pair_offsets + 1, n, S->d_sums);
     }
     hipLaunchKernelGGL(cluster_scan_sums_kernel, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles, d_pair_offsets, S->cand.d);
     if (n) {
         hipLaunchKernelGGL(cluster_apply_kernel, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, d_pair_offsets + 1, n, (const uint64_t*)S->d_sums);
-        hipLaunchKernelGGL(cluster_write_kernel, dim3(grid_of(n, EMIT_WAVES, EMIT_MAX_GRID)), dim3(64 * EMIT_WAVES), 0, st, E);
+        hipLaunchKernelGGL(cluster_write_kernel, dim3(ck_grid_of(n, EMIT_WAVES, EMIT_MAX_GRID)), dim3(64 * EMIT_WAVES), 0, st, E);
     }
     CK_HIP(c, hipGetLastError());
     if ((rc = ck_totals_fetch(c, &S->cand, C_WORDS))) return rc;
@@ -224,16 +192,16 @@ int launch_link(circkit_ctx* c, ClusterState* S, uint64_t n, const uint32_t* d_p
                 const circkit_cluster_params& p, uint64_t* d_labels)
 {
     int rc;
-    if ((rc = ck_grow(c, &S->d_parent, &S->cap_parent, n ? n : 1))) return rc;
+    if ((rc = S->d_parent.grow(c, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if ((rc = ck_totals_clear(c, &S->link, L_WORDS))) return rc;
     Link L;
     L.n_records = n; L.pairs = d_pairs; L.scores = d_scores; L.n_pairs = n_pairs;
     L.min_similarity_q16 = p.min_similarity_q16; L.min_filled = p.min_filled;
     L.parent = S->d_parent; L.labels = d_labels; L.totals = S->link.d;
-    if (n) hipLaunchKernelGGL(cluster_init_kernel, dim3(grid_of(n, LINK_WG, FLATTEN_MAX_GRID)), dim3(LINK_WG), 0, st, L);
-    if (n_pairs) hipLaunchKernelGGL(cluster_link_kernel, dim3(grid_of(n_pairs, LINK_WG, LINK_MAX_GRID)), dim3(LINK_WG), 0, st, L);
-    if (n) hipLaunchKernelGGL(cluster_flatten_kernel, dim3(grid_of(n, LINK_WG, FLATTEN_MAX_GRID)), dim3(LINK_WG), 0, st, L);
+    if (n) hipLaunchKernelGGL(cluster_init_kernel, dim3(ck_grid_of(n, LINK_WG, FLATTEN_MAX_GRID)), dim3(LINK_WG), 0, st, L);
+    if (n_pairs) hipLaunchKernelGGL(cluster_link_kernel, dim3(ck_grid_of(n_pairs, LINK_WG, LINK_MAX_GRID)), dim3(LINK_WG), 0, st, L);
+    if (n) hipLaunchKernelGGL(cluster_flatten_kernel, dim3(ck_grid_of(n, LINK_WG, FLATTEN_MAX_GRID)), dim3(LINK_WG), 0, st, L);
     CK_HIP(c, hipGetLastError());
     if ((rc = ck_totals_fetch(c, &S->link, L_WORDS))) return rc;
     S->any_link = true;
@@ -264,8 +232,8 @@ int circkit_cluster_candidates_device(circkit_ctx* c, const uint64_t* d_sketch, 
     if (capacity >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "capacity too large");
     const uint64_t row_bytes = (n_records << log2_bins) * sizeof(uint64_t), off_bytes = (n_records + 1) * sizeof(uint64_t),
                    pair_bytes = capacity * 2 * sizeof(uint32_t);
-    if (overlap(d_pair_offsets, off_bytes, d_sketch, row_bytes) || overlap(d_pairs, pair_bytes, d_sketch, row_bytes) ||
-        overlap(d_pairs, pair_bytes, d_pair_offsets, off_bytes))
+    if (ck_overlap(d_pair_offsets, off_bytes, d_sketch, row_bytes) || ck_overlap(d_pairs, pair_bytes, d_sketch, row_bytes) ||
+        ck_overlap(d_pairs, pair_bytes, d_pair_offsets, off_bytes))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_pair_offsets / d_pairs overlap the sketch or each other");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     ClusterState* S;
@@ -300,7 +268,7 @@ int circkit_cluster_link_device(circkit_ctx* c, uint64_t n_records, const uint32
     if (((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_scores & 3u) || ((uintptr_t)d_labels & 7u))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_pairs and d_scores must be 4-byte aligned, d_labels 8-byte aligned");
     const uint64_t pair_bytes = n_pairs * 2 * sizeof(uint32_t), label_bytes = n_records * sizeof(uint64_t);
-    if (overlap(d_labels, label_bytes, d_pairs, pair_bytes) || overlap(d_labels, label_bytes, d_scores, pair_bytes))
+    if (ck_overlap(d_labels, label_bytes, d_pairs, pair_bytes) || ck_overlap(d_labels, label_bytes, d_scores, pair_bytes))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_labels overlaps the pairs or the scores");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     ClusterState* S;
@@ -336,11 +304,10 @@ int circkit_cluster_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* 
     if (n_records && (!offsets || !labels)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
     // from the offsets alone, before a payload byte is read
-    for (uint64_t i = 0; i < n_records; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] >= ck_sketch::TOO_LONG)
-            return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was clustered", (unsigned long long)i);
-    }
+    uint64_t at = 0;
+    const ck_csr_fault fault = ck_csr_walk(offsets, n_records, ck_sketch::TOO_LONG, &at);
+    if (fault == CK_CSR_DECREASE) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (fault) return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was clustered", (unsigned long long)at);
     const uint64_t nb = n_records ? offsets[n_records] : 0;
     if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
@@ -348,24 +315,20 @@ int circkit_cluster_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* 
     if ((rc = state(c, &S))) return rc;
     if (n_clusters) *n_clusters = 0;
     const uint64_t n_rows = n_records << sketch->log2_bins, capacity = n_records * params->n_bands;
-    if ((rc = ck_grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_pair_off, &S->cap_pair_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_pairs, &S->cap_pairs, capacity ? 2 * capacity : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_scores, &S->cap_scores, capacity ? 2 * capacity : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_labels, &S->cap_labels, n_records ? n_records : 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
-    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = circkit_sketch_batch_device(c, S->d_bytes, S->d_off, n_records, sketch, S->d_rows, nullptr))) return rc;
+    if ((rc = S->in.upload(c, bytes, offsets, n_records))) return rc;
+    if ((rc = S->d_rows.grow(c, n_rows))) return rc;
+    if ((rc = S->d_pair_off.grow(c, n_records + 1))) return rc;
+    if ((rc = S->d_pairs.grow(c, 2 * capacity))) return rc;
+    if ((rc = S->d_scores.grow(c, 2 * capacity))) return rc;
+    if ((rc = S->d_labels.grow(c, n_records))) return rc;
+    if ((rc = circkit_sketch_batch_device(c, S->in.bytes, S->in.off, n_records, sketch, S->d_rows, nullptr))) return rc;
     if ((rc = launch_candidates(c, S, S->d_rows, n_records, sketch->log2_bins, *params, S->d_pair_off, S->d_pairs, capacity))) return rc;
     // the one wait in the middle: the compare takes the number of pairs from the host
     uint64_t n_pairs = 0;
     if ((rc = circkit_cluster_candidates_status(c, &n_pairs))) return rc;
     if ((rc = circkit_sketch_compare_device(c, S->d_rows, n_records, S->d_rows, n_records, sketch->log2_bins, S->d_pairs, n_pairs, S->d_scores))) return rc;
     if ((rc = launch_link(c, S, n_records, S->d_pairs, S->d_scores, n_pairs, *params, S->d_labels))) return rc;
-    if (n_records) CK_HIP(c, hipMemcpyAsync(labels, S->d_labels, n_records * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = S->d_labels.download(c, labels, n_records))) return rc;
     if ((rc = circkit_sketch_status(c, nullptr, nullptr))) return rc;
     if ((rc = circkit_sketch_compare_status(c, nullptr))) return rc;
     if ((rc = check_link(c, S->link.h))) return rc;

@@ -10,6 +10,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "distance.h"
 
@@ -36,37 +37,15 @@ __global__ __launch_bounds__(64 * DISTANCE_WAVES) void distance_pairs_kernel(Dis
 struct DistanceState {
     ck_totals totals;                // [T_WORDS], of the most recent pairs call
     bool any = false;
-    // the staging of circkit_distance_pairs (grow only)
-    uint8_t* d_bytes[2] = { nullptr, nullptr }; uint64_t cap_bytes[2] = { 0, 0 };
-    uint64_t* d_off[2] = { nullptr, nullptr }; uint64_t cap_off[2] = { 0, 0 };
-    uint32_t* d_pairs = nullptr; uint64_t cap_pairs = 0;
-    uint32_t* d_distance = nullptr; uint64_t cap_distance = 0;
-    uint32_t* d_scores = nullptr; uint64_t cap_scores = 0;
+    // the staging of circkit_distance_pairs
+    ck_csr_buf in[2];
+    ck_buf<uint32_t> d_pairs, d_distance, d_scores;
 };
-
-void release_state(void* p)
-{
-    DistanceState* S = (DistanceState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_bytes[0], S->d_bytes[1], S->d_off[0], S->d_off[1], S->d_pairs, S->d_distance, S->d_scores };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
 
 int state(circkit_ctx* c, DistanceState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_DISTANCE, release_state);
-    if (!*slot) *slot = new DistanceState();
-    DistanceState* S = (DistanceState*)*slot;
-    *out = S;
+    DistanceState* S = *out = ck_unit_state<DistanceState>(c, CK_UNIT_DISTANCE);
     return ck_totals_make(c, &S->totals, T_WORDS);
-}
-
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
 }
 
 int check_params(circkit_ctx* c, const circkit_distance_params* p)
@@ -116,11 +95,10 @@ int check_host_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offse
     if (n >= (1ull << 32)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_a and n_b must be < 2^32");
     if (n && !offsets) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     if (n && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] >= ck_sketch::TOO_LONG)
-            return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: no distance was computed", (unsigned long long)i);
-    }
+    uint64_t at = 0;
+    const ck_csr_fault fault = ck_csr_walk(offsets, n, ck_sketch::TOO_LONG, &at);
+    if (fault == CK_CSR_DECREASE) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (fault) return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: no distance was computed", (unsigned long long)at);
     if (n && offsets[n] && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     return CIRCKIT_OK;
 }
@@ -148,10 +126,10 @@ int circkit_distance_pairs_device(circkit_ctx* c, const uint8_t* d_bytes_a, cons
     const void* outs[2] = { d_out_distance, d_out_scores };
     const uint64_t out_bytes[2] = { dist_bytes, pair_bytes };
     for (int o = 0; o < 2; ++o)
-        if (overlap(outs[o], out_bytes[o], d_offsets_a, off_a_bytes) || overlap(outs[o], out_bytes[o], d_offsets_b, off_b_bytes) ||
-            overlap(outs[o], out_bytes[o], d_pairs, pair_bytes))
+        if (ck_overlap(outs[o], out_bytes[o], d_offsets_a, off_a_bytes) || ck_overlap(outs[o], out_bytes[o], d_offsets_b, off_b_bytes) ||
+            ck_overlap(outs[o], out_bytes[o], d_pairs, pair_bytes))
             return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_distance / d_out_scores overlap the offsets or the pairs");
-    if (overlap(d_out_distance, dist_bytes, d_out_scores, pair_bytes)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_distance overlaps d_out_scores");
+    if (ck_overlap(d_out_distance, dist_bytes, d_out_scores, pair_bytes)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_distance overlaps d_out_scores");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     DistanceState* S;
     if ((rc = state(c, &S))) return rc;
@@ -187,28 +165,18 @@ int circkit_distance_pairs(circkit_ctx* c, const uint8_t* bytes_a, const uint64_
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     DistanceState* S;
     if ((rc = state(c, &S))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    const uint8_t* src_bytes[2] = { bytes_a, bytes_b };
-    const uint64_t* src_off[2] = { offsets_a, offsets_b };
-    const uint64_t n[2] = { n_a, n_b };
-    for (int s = 0; s < (same ? 1 : 2); ++s) {
-        const uint64_t nb = n[s] ? src_off[s][n[s]] : 0;
-        if ((rc = ck_grow(c, &S->d_bytes[s], &S->cap_bytes[s], nb ? nb : 1))) return rc;
-        if ((rc = ck_grow(c, &S->d_off[s], &S->cap_off[s], n[s] + 1))) return rc;
-        if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes[s], src_bytes[s], nb, hipMemcpyHostToDevice, st));
-        if (n[s]) CK_HIP(c, hipMemcpyAsync(S->d_off[s], src_off[s], (n[s] + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    }
-    if ((rc = ck_grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_distance, &S->cap_distance, n_pairs ? n_pairs : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_scores, &S->cap_scores, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if (n_pairs) CK_HIP(c, hipMemcpyAsync(S->d_pairs, pairs, 2 * n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int b = same ? 0 : 1;
-    if ((rc = launch_pairs(c, S, S->d_bytes[0], S->d_off[0], n_a, S->d_bytes[b], S->d_off[b], n_b, *params, S->d_pairs, n_pairs,
-                           out_distance ? S->d_distance : nullptr, out_scores ? S->d_scores : nullptr)))
+    if ((rc = S->in[0].upload(c, bytes_a, offsets_a, n_a))) return rc;
+    if (!same && (rc = S->in[1].upload(c, bytes_b, offsets_b, n_b))) return rc;
+    if ((rc = S->d_pairs.upload(c, pairs, 2 * n_pairs))) return rc;
+    if ((rc = S->d_distance.grow(c, n_pairs))) return rc;
+    if ((rc = S->d_scores.grow(c, 2 * n_pairs))) return rc;
+    const ck_csr_buf& b = S->in[same ? 0 : 1];
+    if ((rc = launch_pairs(c, S, S->in[0].bytes, S->in[0].off, n_a, b.bytes, b.off, n_b, *params, S->d_pairs, n_pairs,
+                           out_distance ? S->d_distance.p : nullptr, out_scores ? S->d_scores.p : nullptr)))
         return rc;
-    if (n_pairs && out_distance) CK_HIP(c, hipMemcpyAsync(out_distance, S->d_distance, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (n_pairs && out_scores) CK_HIP(c, hipMemcpyAsync(out_scores, S->d_scores, 2 * n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
+    if ((rc = S->d_distance.download(c, out_distance, n_pairs))) return rc;
+    if ((rc = S->d_scores.download(c, out_scores, 2 * n_pairs))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     return check_invalid(c, S->totals.h[ck_distance::T_INVALID]);
 }
 

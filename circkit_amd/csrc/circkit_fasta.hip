@@ -163,43 +163,27 @@ __global__ __launch_bounds__(SPANS_WG) void fasta_spans_kernel(const uint8_t* __
 }
 
 struct FastaState {
-    uint8_t* d_lut = nullptr;        // ckhost::normalize_lut(), copied when the slot is made
+    ck_buf<uint8_t> d_lut;           // ckhost::normalize_lut(), copied when the slot is made
     ck_totals totals;                // [T_WORDS], made with the state
     uint64_t byte_capacity = 0, record_capacity = 0;       // of the most recent parse, for the status message
     bool any = false;
-    Summary* d_summaries = nullptr; uint64_t cap_summaries = 0;
-    Prefix* d_prefix = nullptr; uint64_t cap_prefix = 0;
-    Span* d_spare = nullptr; uint64_t cap_spare = 0;       // stands in for the one of d_head / d_raw that was not given
-    // the staging of circkit_fasta_parse_text (grow only)
-    uint8_t* d_text = nullptr; uint64_t cap_text = 0;
-    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    Span* d_head = nullptr; uint64_t cap_head = 0;
-    Span* d_raw = nullptr; uint64_t cap_raw = 0;
+    ck_buf<Summary> d_summaries;
+    ck_buf<Prefix> d_prefix;
+    ck_buf<Span> d_spare;            // stands in for the one of d_head / d_raw that was not given
+    // the staging of circkit_fasta_parse_text
+    ck_buf<uint8_t> d_text, d_out;
+    ck_buf<uint64_t> d_off;
+    ck_buf<Span> d_head, d_raw;
 };
-
-void release_state(void* p)
-{
-    FastaState* S = (FastaState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_lut, S->d_summaries, S->d_prefix, S->d_spare, S->d_text, S->d_out, S->d_off, S->d_head, S->d_raw };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
 
 int state(circkit_ctx* c, FastaState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_FASTA, release_state);
-    if (!*slot) *slot = new FastaState();
-    FastaState* S = (FastaState*)*slot;
-    *out = S;
+    FastaState* S = *out = ck_unit_state<FastaState>(c, CK_UNIT_FASTA);
+    int rc;
     if (!S->d_lut) {
-        uint8_t* lut = nullptr;
-        CK_HIP(c, hipMalloc((void**)&lut, 256));
-        hipError_t e = hipMemcpy(lut, ckhost::normalize_lut(), 256, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(lut); CK_HIP(c, e); }
-        S->d_lut = lut;
+        if ((rc = S->d_lut.grow(c, 256))) return rc;
+        hipError_t e = hipMemcpy(S->d_lut, ckhost::normalize_lut(), 256, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { S->d_lut.release(); CK_HIP(c, e); }
     }
     return ck_totals_make(c, &S->totals, T_WORDS);
 }
@@ -212,11 +196,11 @@ int launch_parse(circkit_ctx* c, FastaState* S, const uint8_t* d_text, uint64_t 
 {
     const uint64_t tiles = (n + ck_fasta::TILE_BYTES - 1) / ck_fasta::TILE_BYTES;
     int rc;
-    if ((rc = ck_grow(c, &S->d_summaries, &S->cap_summaries, tiles ? tiles : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_prefix, &S->cap_prefix, tiles ? tiles : 1))) return rc;
+    if ((rc = S->d_summaries.grow(c, tiles))) return rc;
+    if ((rc = S->d_prefix.grow(c, tiles))) return rc;
     if ((d_head != nullptr) != (d_raw != nullptr)) {
         const uint64_t most = most_records(n), spare = record_capacity < most ? record_capacity : most;
-        if ((rc = ck_grow(c, &S->d_spare, &S->cap_spare, spare ? spare : 1))) return rc;
+        if ((rc = S->d_spare.grow(c, spare))) return rc;
         if (!d_head) d_head = S->d_spare; else d_raw = S->d_spare;
     }
     const uint32_t flags = (first_chunk ? FLAG_FIRST : 0) | (final_chunk ? FLAG_FINAL : 0);
@@ -311,15 +295,14 @@ int circkit_fasta_parse_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     // no text needs more than this, whatever the caller's buffers hold
     const uint64_t most = most_records(n_text);
     const uint64_t bytes_cap = byte_capacity < n_text ? byte_capacity : n_text, records_cap = record_capacity < most ? record_capacity : most;
-    if ((rc = ck_grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, bytes_cap ? bytes_cap : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, records_cap + 1))) return rc;
-    if (head && (rc = ck_grow(c, &S->d_head, &S->cap_head, records_cap ? records_cap : 1))) return rc;
-    if (raw && (rc = ck_grow(c, &S->d_raw, &S->cap_raw, records_cap ? records_cap : 1))) return rc;
+    if ((rc = S->d_text.upload(c, text, n_text))) return rc;
+    if ((rc = S->d_out.grow(c, bytes_cap))) return rc;
+    if ((rc = S->d_off.grow(c, records_cap + 1))) return rc;
+    if (head && (rc = S->d_head.grow(c, records_cap))) return rc;
+    if (raw && (rc = S->d_raw.grow(c, records_cap))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (n_text) CK_HIP(c, hipMemcpyAsync(S->d_text, text, n_text, hipMemcpyHostToDevice, st));
-    if ((rc = launch_parse(c, S, S->d_text, n_text, first_chunk, final_chunk, S->d_out, bytes_cap, S->d_off, records_cap, head ? S->d_head : nullptr,
-                           raw ? S->d_raw : nullptr)))
+    if ((rc = launch_parse(c, S, S->d_text, n_text, first_chunk, final_chunk, S->d_out, bytes_cap, S->d_off, records_cap, head ? S->d_head.p : nullptr,
+                           raw ? S->d_raw.p : nullptr)))
         return rc;
     S->byte_capacity = byte_capacity;
     S->record_capacity = record_capacity;
@@ -332,10 +315,10 @@ int circkit_fasta_parse_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     if (consumed) *consumed = t[T_CONSUMED];
     out_offsets[0] = 0;
     if (t[T_REFUSED]) return check_totals(c, S, t);
-    if (B) CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
-    if (R) CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_off, (R + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (R && head) CK_HIP(c, hipMemcpyAsync(head, S->d_head, R * sizeof(Span), hipMemcpyDeviceToHost, st));
-    if (R && raw) CK_HIP(c, hipMemcpyAsync(raw, S->d_raw, R * sizeof(Span), hipMemcpyDeviceToHost, st));
+    if ((rc = S->d_out.download(c, out_bytes, B))) return rc;
+    if (R && (rc = S->d_off.download(c, out_offsets, R + 1))) return rc;
+    if ((rc = S->d_head.download(c, (Span*)head, R))) return rc;
+    if ((rc = S->d_raw.download(c, (Span*)raw, R))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     return CIRCKIT_OK;
 }

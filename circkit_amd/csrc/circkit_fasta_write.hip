@@ -17,6 +17,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "ck_scan.h"
 #include "fasta_write.h"
@@ -102,35 +103,18 @@ struct WriteState {
     ck_totals totals;                // [T_WORDS], made with the state
     uint64_t capacity = 0;           // of the most recent write, for the status message
     bool any = false;
-    uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
-    // the staging of circkit_fasta_write_text (grow only)
-    uint8_t* d_text = nullptr; uint64_t cap_text = 0;
-    Span* d_head = nullptr; uint64_t cap_head = 0;
-    Span* d_raw = nullptr; uint64_t cap_raw = 0;
-    uint64_t* d_src = nullptr; uint64_t cap_src = 0;
-    Label* d_labels = nullptr; uint64_t cap_labels = 0;
-    uint8_t* d_body = nullptr; uint64_t cap_body = 0;
-    uint64_t* d_body_off = nullptr; uint64_t cap_body_off = 0;
-    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
-    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
+    ck_buf<uint64_t> d_sums;
+    // the staging of circkit_fasta_write_text
+    ck_buf<uint8_t> d_text, d_out;
+    ck_buf<Span> d_head, d_raw;
+    ck_buf<uint64_t> d_src, d_out_off;
+    ck_buf<Label> d_labels;
+    ck_csr_buf body;
 };
-
-void release_state(void* p)
-{
-    WriteState* S = (WriteState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_sums, S->d_text, S->d_head, S->d_raw, S->d_src, S->d_labels, S->d_body, S->d_body_off, S->d_out_off, S->d_out };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
 
 int state(circkit_ctx* c, WriteState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_FASTA_WRITE, release_state);
-    if (!*slot) *slot = new WriteState();
-    WriteState* S = (WriteState*)*slot;
-    *out = S;
+    WriteState* S = *out = ck_unit_state<WriteState>(c, CK_UNIT_FASTA_WRITE);
     return ck_totals_make(c, &S->totals, T_WORDS);
 }
 
@@ -154,7 +138,7 @@ int launch_offsets(circkit_ctx* c, WriteState* S, const Source& src, uint64_t m,
 {
     const uint64_t tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
     int rc;
-    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = S->d_sums.grow(c, tiles))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if ((rc = ck_totals_clear(c, &S->totals, T_WORDS))) return rc;
     if (m) {
@@ -250,46 +234,39 @@ int circkit_fasta_write_text(circkit_ctx* c, const uint8_t* text, uint64_t n_tex
     // the body as far as its offsets reach: they must not decrease, so that the last one is the payload's end
     uint64_t nb = 0;
     if (body_offsets) {
-        for (uint64_t k = 0; k < n_out; ++k)
-            if (body_offsets[k + 1] < body_offsets[k]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "body_offsets must not decrease");
+        uint64_t at = 0;
+        if (ck_csr_walk(body_offsets, n_out, CK_CSR_NO_LIMIT, &at)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "body_offsets must not decrease");
         nb = body_offsets[n_out];
         if (nb >= (1ull << 48)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "body_offsets too large");
     }
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     WriteState* S;
     if ((rc = state(c, &S))) return rc;
-    if ((rc = ck_grow(c, &S->d_text, &S->cap_text, n_text ? n_text : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_head, &S->cap_head, n_heads ? n_heads : 1))) return rc;
-    if (raw && (rc = ck_grow(c, &S->d_raw, &S->cap_raw, n_heads ? n_heads : 1))) return rc;
-    if (src && (rc = ck_grow(c, &S->d_src, &S->cap_src, n_src ? n_src : 1))) return rc;
-    if (labels && (rc = ck_grow(c, &S->d_labels, &S->cap_labels, n_out ? n_out : 1))) return rc;
-    if (body && (rc = ck_grow(c, &S->d_body, &S->cap_body, nb ? nb : 1))) return rc;
-    if (body && (rc = ck_grow(c, &S->d_body_off, &S->cap_body_off, n_out + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_out + 1))) return rc;
+    if ((rc = S->d_text.upload(c, text, n_text))) return rc;
+    if ((rc = S->d_head.upload(c, (const Span*)head, n_heads))) return rc;
+    if (raw && (rc = S->d_raw.upload(c, (const Span*)raw, n_heads))) return rc;
+    if (src && (rc = S->d_src.upload(c, src, n_src))) return rc;
+    if (labels && (rc = S->d_labels.upload(c, (const Label*)labels, n_out))) return rc;
+    if (body && (rc = S->body.bytes.upload(c, body, nb))) return rc;
+    if (body && (rc = S->body.off.upload(c, body_offsets, n_out + 1))) return rc;      // (all n_out + 1 of them, of no record too)
+    if ((rc = S->d_out_off.grow(c, n_out + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (n_text) CK_HIP(c, hipMemcpyAsync(S->d_text, text, n_text, hipMemcpyHostToDevice, st));
-    if (n_heads && head) CK_HIP(c, hipMemcpyAsync(S->d_head, head, n_heads * sizeof(Span), hipMemcpyHostToDevice, st));
-    if (n_heads && raw) CK_HIP(c, hipMemcpyAsync(S->d_raw, raw, n_heads * sizeof(Span), hipMemcpyHostToDevice, st));
-    if (n_src && src) CK_HIP(c, hipMemcpyAsync(S->d_src, src, n_src * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_out && labels) CK_HIP(c, hipMemcpyAsync(S->d_labels, labels, n_out * sizeof(Label), hipMemcpyHostToDevice, st));
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_body, body, nb, hipMemcpyHostToDevice, st));
-    if (body) CK_HIP(c, hipMemcpyAsync(S->d_body_off, body_offsets, (n_out + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    const Source dev = source_of(S->d_text, n_text, (const circkit_fasta_span*)S->d_head, raw ? (const circkit_fasta_span*)S->d_raw : nullptr, n_heads,
-                                 src ? S->d_src : nullptr, n_src, labels ? (const circkit_window*)S->d_labels : nullptr, body ? S->d_body : nullptr,
-                                 body ? S->d_body_off : nullptr);
+    const Source dev = source_of(S->d_text, n_text, (const circkit_fasta_span*)S->d_head.p, raw ? (const circkit_fasta_span*)S->d_raw.p : nullptr, n_heads,
+                                 src ? S->d_src.p : nullptr, n_src, labels ? (const circkit_window*)S->d_labels.p : nullptr,
+                                 body ? S->body.bytes.p : nullptr, body ? S->body.off.p : nullptr);
     // the offsets first: the staging for the text is sized by the total they end in (it cannot overlap the staged inputs)
     if ((rc = launch_offsets(c, S, dev, n_out, nullptr, out_capacity, S->d_out_off))) return rc;
     if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
-    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_out + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = S->d_out_off.download(c, out_offsets, n_out + 1))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     const uint64_t B = S->totals.h[T_TOTAL];
     if (total) *total = B;
     if (S->totals.h[T_REFUSED]) return check_totals(c, S->totals.h, out_capacity);
     if (B) {
         if (!out_text) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
+        if ((rc = S->d_out.grow(c, B))) return rc;
         if ((rc = launch_write(c, S, dev, n_out, S->d_out_off, S->d_out))) return rc;
-        CK_HIP(c, hipMemcpyAsync(out_text, S->d_out, B, hipMemcpyDeviceToHost, st));
+        if ((rc = S->d_out.download(c, out_text, B))) return rc;
         CK_HIP(c, hipStreamSynchronize(st));
     }
     return check_totals(c, S->totals.h, out_capacity);

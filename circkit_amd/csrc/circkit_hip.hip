@@ -66,8 +66,7 @@ int circkit_ctx_destroy(circkit_ctx* c)
     if (!c) return CIRCKIT_OK;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    void* ptrs[] = { c->d_comp, c->d_counters, c->d_seg_counts, c->d_in, c->d_out, c->d_strand, c->d_off, c->d_idx, c->d_hash,
-                     c->d_view, c->d_hashed, c->d_gscratch };
+    void* ptrs[] = { c->d_comp, c->d_counters, c->d_seg_counts, c->d_in, c->d_out, c->d_strand, c->d_off, c->d_idx, c->d_hash };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (uint32_t* p : c->d_lists) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -82,7 +81,7 @@ int circkit_ctx_destroy(circkit_ctx* c)
     if (c->h_off) (void)hipHostFree((void*)c->h_off);
     for (auto& u : c->units) if (u.release) u.release(u.p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                            // (with its ck_bufs)
     return CIRCKIT_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"            // the ctx lives in circkit_hip.hip; this file sees it through this header
 #include "ck_compact_launch.h"
 #include "ck_scan.h"
@@ -149,40 +150,31 @@ __global__ __launch_bounds__(64 * ck_compact::GATHER_WAVES) void compact_gather_
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) ck_compact::gather_tile(G, t);
 }
 
-struct MonoState {                   // host-buffer form staging (grow only)
-    uint8_t* d_in = nullptr; uint64_t cap_in = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    uint32_t* d_end = nullptr; uint64_t cap_end = 0;
+struct MonoState {                   // host-buffer form staging
+    ck_csr_buf in;
+    ck_buf<uint32_t> d_end;
     // compact: scan scratch, the totals on the device and their pinned copy
-    uint64_t* d_w = nullptr; uint64_t cap_w = 0;
-    Pair* d_sums = nullptr; uint64_t cap_sums = 0;
-    uint64_t* d_src_start = nullptr; uint64_t cap_src_start = 0;
+    ck_buf<uint64_t> d_w, d_src_start;
+    ck_buf<Pair> d_sums;
     ck_totals totals;                // [T_WORDS], made at the first compact
     bool host_last = false;          // the last compact was the host form: its totals are host_totals
     uint64_t host_totals[T_WORDS] = { 0, 0, 0 };
     // compact, host-buffer form staging
-    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
-    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
-    uint64_t* d_out_src = nullptr; uint64_t cap_out_src = 0;
-    uint32_t* d_kept = nullptr; uint64_t cap_kept = 0;
-    uint64_t* d_full = nullptr; uint64_t cap_full = 0;
+    ck_buf<uint8_t> d_out;
+    ck_buf<uint64_t> d_out_off, d_out_src, d_full;
+    ck_buf<uint32_t> d_kept;
 };
 
-void release_state(void* p)
-{
-    MonoState* S = (MonoState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_in, S->d_off, S->d_end, S->d_w, S->d_sums, S->d_src_start, S->d_out, S->d_out_off, S->d_out_src, S->d_kept, S->d_full };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
+MonoState* state(circkit_ctx* c) { return ck_unit_state<MonoState>(c, CK_UNIT_MONOMERIZE); }
 
-MonoState* state(circkit_ctx* c)
+// the walk both host forms make behind their params: the unit takes records below 2^32 symbols
+int check_offsets(circkit_ctx* c, const uint64_t* offsets, uint64_t n)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_MONOMERIZE, release_state);
-    if (!*slot) *slot = new MonoState();
-    return (MonoState*)*slot;
+    uint64_t at = 0;
+    const ck_csr_fault fault = ck_csr_walk(offsets, n, 1ull << 32, &at);
+    if (fault == CK_CSR_DECREASE) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (fault) return ck_ctx_fail(c, CIRCKIT_ERR_TOO_LONG, "a record of 2^32 symbols or more");
+    return CIRCKIT_OK;
 }
 
 // MonomerizerBuilder::validate (lib/src/monomerize.rs:20-40) + the CLI's range check of the identity (src/monomerize.rs:40-44)
@@ -249,9 +241,9 @@ int ck_compact_reserve(circkit_ctx* c, uint64_t n, uint64_t** d_w)
     MonoState* S = state(c);
     const uint64_t tiles = (n + CSCAN_TILE - 1) / CSCAN_TILE;
     int rc;
-    if ((rc = ck_grow(c, &S->d_w, &S->cap_w, n ? n : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_src_start, &S->cap_src_start, n ? n : 1))) return rc;
+    if ((rc = S->d_w.grow(c, n))) return rc;
+    if ((rc = S->d_sums.grow(c, tiles))) return rc;
+    if ((rc = S->d_src_start.grow(c, n))) return rc;
     *d_w = S->d_w;
     return CIRCKIT_OK;
 }
@@ -303,23 +295,15 @@ int circkit_monomerize_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_
     ck_mono::Params P;
     int rc = make_params(c, params, &P);
     if (rc) return rc;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_TOO_LONG, "a record of 2^32 symbols or more");
-    }
+    if ((rc = check_offsets(c, offsets, n))) return rc;
     if (n == 0) return CIRCKIT_OK;
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     MonoState* S = state(c);
-    const uint64_t nb = offsets[n];
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_end, &S->cap_end, n))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = launch(c, S->d_in, S->d_off, n, P, S->d_end))) return rc;
-    CK_HIP(c, hipMemcpyAsync(end, S->d_end, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
+    if ((rc = S->in.upload(c, bytes, offsets, n))) return rc;
+    if ((rc = S->d_end.grow(c, n))) return rc;
+    if ((rc = launch(c, S->in.bytes, S->in.off, n, P, S->d_end))) return rc;
+    if ((rc = S->d_end.download(c, end, n))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     return CIRCKIT_OK;
 }
 
@@ -375,10 +359,7 @@ int circkit_monomers_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     ck_mono::Params P;
     int rc = make_params(c, params, &P);
     if (rc) return rc;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_TOO_LONG, "a record of 2^32 symbols or more");
-    }
+    if ((rc = check_offsets(c, offsets, n))) return rc;
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     MonoState* S = state(c);
     out_offsets[0] = 0;
@@ -387,30 +368,26 @@ int circkit_monomers_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     S->host_totals[T_RECORDS] = S->host_totals[T_BYTES] = S->host_totals[T_OVERLAP] = 0;
     if (n == 0) return CIRCKIT_OK;
     const uint64_t nb = offsets[n];
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_end, &S->cap_end, n))) return rc;
-    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
-    if ((rc = ck_grow(c, &S->d_kept, &S->cap_kept, n))) return rc;
-    if (full_len && (rc = ck_grow(c, &S->d_full, &S->cap_full, n))) return rc;
+    if ((rc = S->in.upload(c, bytes, offsets, n))) return rc;
+    if ((rc = S->d_end.grow(c, n))) return rc;
+    if ((rc = S->d_out.grow(c, nb))) return rc;
+    if ((rc = S->d_out_off.grow(c, n + 1))) return rc;
+    if ((rc = S->d_out_src.grow(c, n))) return rc;
+    if ((rc = S->d_kept.grow(c, n))) return rc;
+    if (full_len && (rc = S->d_full.upload(c, full_len, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (full_len) CK_HIP(c, hipMemcpyAsync(S->d_full, full_len, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = launch(c, S->d_in, S->d_off, n, P, S->d_end))) return rc;
-    if ((rc = launch_compact(c, S, S->d_in, S->d_off, n, S->d_end, full_len ? S->d_full : nullptr, filter, S->d_out, S->d_out_off,
+    if ((rc = launch(c, S->in.bytes, S->in.off, n, P, S->d_end))) return rc;
+    if ((rc = launch_compact(c, S, S->in.bytes, S->in.off, n, S->d_end, full_len ? S->d_full.p : nullptr, filter, S->d_out, S->d_out_off,
                              S->d_out_src, S->d_kept))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     S->host_last = true;
     for (int k = 0; k < T_WORDS; ++k) S->host_totals[k] = S->totals.h[k];
     if ((rc = check_totals(c, S->host_totals))) return rc;
     const uint64_t m = S->host_totals[T_RECORDS], B = S->host_totals[T_BYTES];
-    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (m) CK_HIP(c, hipMemcpyAsync(out_src, S->d_out_src, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (kept_end) CK_HIP(c, hipMemcpyAsync(kept_end, S->d_kept, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (B) CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
+    if ((rc = S->d_out_off.download(c, out_offsets, m + 1))) return rc;
+    if ((rc = S->d_out_src.download(c, out_src, m))) return rc;
+    if ((rc = S->d_kept.download(c, kept_end, n))) return rc;
+    if ((rc = S->d_out.download(c, out_bytes, B))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     if (n_kept) *n_kept = m;
     return CIRCKIT_OK;

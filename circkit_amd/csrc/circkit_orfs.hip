@@ -111,30 +111,15 @@ struct OrfState {
     uint64_t capacity = 0;
     bool host_last = false;           // the last batch was the host form: its total is host_total
     uint64_t host_total = 0;
-    uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
-    // host-buffer form staging (grow only)
-    uint8_t* d_in = nullptr; uint64_t cap_in = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_rec = 0;
-    uint64_t* d_orf_off = nullptr; uint64_t cap_orf_off = 0;
-    Orf* d_orfs = nullptr; uint64_t cap_orfs = 0;
+    ck_buf<uint64_t> d_sums;
+    // host-buffer form staging
+    ck_csr_buf in;
+    ck_buf<uint64_t> d_orf_off;
+    ck_buf<Orf> d_orfs;
+    ~OrfState() { if (h_total) (void)hipHostFree(h_total); }
 };
 
-void release_state(void* p)
-{
-    OrfState* S = (OrfState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_sums, S->d_in, S->d_off, S->d_orf_off, S->d_orfs };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (S->h_total) (void)hipHostFree(S->h_total);
-    delete S;
-}
-
-OrfState* state(circkit_ctx* c)
-{
-    void** slot = ck_ctx_slot(c, CK_UNIT_ORFS, release_state);
-    if (!*slot) *slot = new OrfState();
-    return (OrfState*)*slot;
-}
+OrfState* state(circkit_ctx* c) { return ck_unit_state<OrfState>(c, CK_UNIT_ORFS); }
 
 int make_args(circkit_ctx* c, const circkit_orf_params* p, OrfArgs* A)
 {
@@ -172,7 +157,7 @@ int launch_count(circkit_ctx* c, OrfState* S, const uint8_t* d_bytes, const uint
     CK_HIP(c, hipGetLastError());
     if (n == 0) return CIRCKIT_OK;
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    int rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles);
+    int rc = S->d_sums.grow(c, tiles);
     if (rc) return rc;
     hipLaunchKernelGGL(scan_tile_sums, dim3((uint32_t)tiles), dim3(SCAN_WG), 0, st, (const uint64_t*)d_orf_offsets + 1, n, S->d_sums);
     hipLaunchKernelGGL(scan_sums, dim3(1), dim3(SCAN_WG), 0, st, S->d_sums, tiles);
@@ -244,15 +229,11 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     if (rc) return rc;
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     OrfState* S = state(c);
-    const uint64_t nb = offsets[n];
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_rec, n + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_orf_off, &S->cap_orf_off, n + 1))) return rc;
+    if ((rc = S->in.upload(c, bytes, offsets, n))) return rc;        // (of an empty batch no offset is read)
+    if ((rc = S->d_orf_off.grow(c, n + 1))) return rc;
     hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = launch_count(c, S, S->d_in, S->d_off, n, A, S->d_orf_off))) return rc;
-    CK_HIP(c, hipMemcpyAsync(orf_offsets, S->d_orf_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if ((rc = launch_count(c, S, S->in.bytes, S->in.off, n, A, S->d_orf_off))) return rc;
+    if ((rc = S->d_orf_off.download(c, orf_offsets, n + 1))) return rc;
     CK_HIP(c, hipStreamSynchronize(st));
     const uint64_t t = orf_offsets[n];
     if (total) *total = t;
@@ -263,9 +244,9 @@ int circkit_orfs_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         return ck_ctx_fail(c, CIRCKIT_ERR_OOM, m);
     }
     if (t == 0) return CIRCKIT_OK;
-    if ((rc = ck_grow(c, &S->d_orfs, &S->cap_orfs, t))) return rc;
-    if ((rc = launch_emit(c, S->d_in, S->d_off, n, A, S->d_orf_off, S->d_orfs, t))) return rc;
-    CK_HIP(c, hipMemcpyAsync(orfs, S->d_orfs, t * sizeof(Orf), hipMemcpyDeviceToHost, st));
+    if ((rc = S->d_orfs.grow(c, t))) return rc;
+    if ((rc = launch_emit(c, S->in.bytes, S->in.off, n, A, S->d_orf_off, S->d_orfs, t))) return rc;
+    CK_HIP(c, hipMemcpyAsync(orfs, S->d_orfs, t * sizeof(Orf), hipMemcpyDeviceToHost, st));      // (a null orfs is HIP's to refuse)
     CK_HIP(c, hipStreamSynchronize(st));
     return CIRCKIT_OK;
 }

@@ -11,6 +11,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "prealign.h"
 
@@ -43,45 +44,17 @@ __global__ __launch_bounds__(LABELS_WG) void prealign_labels_kernel(const uint64
 struct PrealignState {
     ck_totals totals;                // [T_WORDS], of the most recent pairs call
     bool any = false;
-    // the staging of circkit_prealign_batch (grow only)
-    uint8_t* d_bytes = nullptr; uint64_t cap_bytes = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    uint64_t* d_rows = nullptr; uint64_t cap_rows = 0;
-    uint32_t* d_anchors = nullptr; uint64_t cap_anchors = 0;
-    uint32_t* d_pairs = nullptr; uint64_t cap_pairs = 0;
-    uint32_t* d_scores = nullptr; uint64_t cap_scores = 0;
-    circkit_window* d_windows = nullptr; uint64_t cap_windows = 0;
+    // the staging of circkit_prealign_batch
+    ck_csr_buf in;
+    ck_buf<uint64_t> d_rows;
+    ck_buf<uint32_t> d_anchors, d_pairs, d_scores;
+    ck_buf<circkit_window> d_windows;
 };
-
-void release_state(void* p)
-{
-    PrealignState* S = (PrealignState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_bytes, S->d_off, S->d_rows, S->d_anchors, S->d_pairs, S->d_scores, S->d_windows };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
 
 int state(circkit_ctx* c, PrealignState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_PREALIGN, release_state);
-    if (!*slot) *slot = new PrealignState();
-    PrealignState* S = (PrealignState*)*slot;
-    *out = S;
+    PrealignState* S = *out = ck_unit_state<PrealignState>(c, CK_UNIT_PREALIGN);
     return ck_totals_make(c, &S->totals, T_WORDS);
-}
-
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-uint32_t grid_of(uint64_t work, uint32_t per_block, uint32_t max_grid)
-{
-    const uint64_t blocks = (work + per_block - 1) / per_block;
-    return (uint32_t)(blocks > max_grid ? max_grid : blocks);
 }
 
 int check_params(circkit_ctx* c, const circkit_prealign_params* p)
@@ -109,7 +82,7 @@ int launch_pairs(circkit_ctx* c, PrealignState* S, const uint64_t* d_sketch, con
         P.pairs = d_pairs; P.n_pairs = n_pairs;
         P.windows = (uint8_t*)d_windows; P.scores = d_scores; P.totals = S->totals.d;
         const size_t lds = ((size_t)PREALIGN_WAVES << p.log2_bins) * sizeof(uint32_t);
-        hipLaunchKernelGGL(prealign_pairs_kernel, dim3(grid_of(n_pairs, PREALIGN_WAVES, PAIRS_MAX_GRID)), dim3(64 * PREALIGN_WAVES), lds, st, P);
+        hipLaunchKernelGGL(prealign_pairs_kernel, dim3(ck_grid_of(n_pairs, PREALIGN_WAVES, PAIRS_MAX_GRID)), dim3(64 * PREALIGN_WAVES), lds, st, P);
         CK_HIP(c, hipGetLastError());
     }
     if ((rc = ck_totals_fetch(c, &S->totals, T_WORDS))) return rc;
@@ -148,10 +121,10 @@ int circkit_prealign_pairs_device(circkit_ctx* c, const uint64_t* d_sketch, cons
     const void* outs[2] = { d_windows, d_scores };
     const uint64_t out_bytes[2] = { window_bytes, pair_bytes };
     for (int o = 0; o < 2; ++o)
-        if (overlap(outs[o], out_bytes[o], d_sketch, row_bytes) || overlap(outs[o], out_bytes[o], d_anchors, anchor_bytes) ||
-            overlap(outs[o], out_bytes[o], d_offsets, off_bytes) || overlap(outs[o], out_bytes[o], d_pairs, pair_bytes))
+        if (ck_overlap(outs[o], out_bytes[o], d_sketch, row_bytes) || ck_overlap(outs[o], out_bytes[o], d_anchors, anchor_bytes) ||
+            ck_overlap(outs[o], out_bytes[o], d_offsets, off_bytes) || ck_overlap(outs[o], out_bytes[o], d_pairs, pair_bytes))
             return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_windows / d_scores overlap an input");
-    if (overlap(d_windows, window_bytes, d_scores, pair_bytes)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_windows overlaps d_scores");
+    if (ck_overlap(d_windows, window_bytes, d_scores, pair_bytes)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_windows overlaps d_scores");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     PrealignState* S;
     if ((rc = state(c, &S))) return rc;
@@ -179,11 +152,11 @@ int circkit_prealign_pairs_of_labels_device(circkit_ctx* c, const uint64_t* d_la
     if (n_records && (!d_labels || !d_pairs)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     if (((uintptr_t)d_labels & 7u) || ((uintptr_t)d_pairs & 3u))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_labels must be 8-byte aligned, d_pairs 4-byte aligned");
-    if (overlap(d_pairs, n_records * 2 * sizeof(uint32_t), d_labels, n_records * sizeof(uint64_t)))
+    if (ck_overlap(d_pairs, n_records * 2 * sizeof(uint32_t), d_labels, n_records * sizeof(uint64_t)))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_pairs overlaps d_labels");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     if (n_records) {
-        hipLaunchKernelGGL(prealign_labels_kernel, dim3(grid_of(n_records, LABELS_WG, LABELS_MAX_GRID)), dim3(LABELS_WG), 0, ck_ctx_stream(c), d_labels,
+        hipLaunchKernelGGL(prealign_labels_kernel, dim3(ck_grid_of(n_records, LABELS_WG, LABELS_MAX_GRID)), dim3(LABELS_WG), 0, ck_ctx_stream(c), d_labels,
                            n_records, d_pairs);
         CK_HIP(c, hipGetLastError());
     }
@@ -205,34 +178,26 @@ int circkit_prealign_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
     if ((n_records && !offsets) || (n_pairs && (!pairs || !windows || !scores))) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
     // from the offsets alone, before a payload byte is read
-    for (uint64_t i = 0; i < n_records; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] >= ck_sketch::TOO_LONG)
-            return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was aligned", (unsigned long long)i);
-    }
+    uint64_t at = 0;
+    const ck_csr_fault fault = ck_csr_walk(offsets, n_records, ck_sketch::TOO_LONG, &at);
+    if (fault == CK_CSR_DECREASE) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (fault) return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was aligned", (unsigned long long)at);
     const uint64_t nb = n_records ? offsets[n_records] : 0;
     if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     PrealignState* S;
     if ((rc = state(c, &S))) return rc;
     const uint64_t n_rows = n_records << sketch->log2_bins;
-    if ((rc = ck_grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_anchors, &S->cap_anchors, n_rows ? n_rows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_scores, &S->cap_scores, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_windows, &S->cap_windows, n_pairs ? n_pairs : 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
-    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_pairs) CK_HIP(c, hipMemcpyAsync(S->d_pairs, pairs, 2 * n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if ((rc = circkit_sketch_anchors_device(c, S->d_bytes, S->d_off, n_records, sketch, S->d_rows, nullptr, S->d_anchors))) return rc;
-    if ((rc = launch_pairs(c, S, S->d_rows, S->d_anchors, S->d_off, n_records, p, S->d_pairs, n_pairs, S->d_windows, S->d_scores))) return rc;
-    if (n_pairs) {
-        CK_HIP(c, hipMemcpyAsync(windows, S->d_windows, n_pairs * sizeof(circkit_window), hipMemcpyDeviceToHost, st));
-        CK_HIP(c, hipMemcpyAsync(scores, S->d_scores, 2 * n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
+    if ((rc = S->in.upload(c, bytes, offsets, n_records))) return rc;
+    if ((rc = S->d_rows.grow(c, n_rows))) return rc;
+    if ((rc = S->d_anchors.grow(c, n_rows))) return rc;
+    if ((rc = S->d_pairs.upload(c, pairs, 2 * n_pairs))) return rc;
+    if ((rc = S->d_scores.grow(c, 2 * n_pairs))) return rc;
+    if ((rc = S->d_windows.grow(c, n_pairs))) return rc;
+    if ((rc = circkit_sketch_anchors_device(c, S->in.bytes, S->in.off, n_records, sketch, S->d_rows, nullptr, S->d_anchors))) return rc;
+    if ((rc = launch_pairs(c, S, S->d_rows, S->d_anchors, S->in.off, n_records, p, S->d_pairs, n_pairs, S->d_windows, S->d_scores))) return rc;
+    if ((rc = S->d_windows.download(c, windows, n_pairs))) return rc;
+    if ((rc = S->d_scores.download(c, scores, 2 * n_pairs))) return rc;
     if ((rc = circkit_sketch_status(c, nullptr, nullptr))) return rc;   // (waits for the stream)
     return check_invalid(c, S->totals.h[ck_prealign::T_INVALID]);
 }

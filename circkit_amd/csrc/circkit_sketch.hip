@@ -16,6 +16,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "sketch.h"
 
@@ -67,43 +68,19 @@ struct SketchState {
     ck_totals totals;                // [T_WORDS], of the most recent sketch; both made with the state
     ck_totals invalid;               // [1]: the invalid pairs of the most recent compare
     bool any = false, any_compare = false;
-    uint64_t* d_long = nullptr; uint64_t cap_long = 0;          // the list of long records (grow only, n_records entries)
-    // the staging of the host forms (grow only)
-    uint8_t* d_bytes = nullptr; uint64_t cap_bytes = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    uint64_t* d_rows = nullptr; uint64_t cap_rows = 0;
-    uint32_t* d_counts = nullptr; uint64_t cap_counts = 0;
-    uint64_t* d_rows_b = nullptr; uint64_t cap_rows_b = 0;
-    uint32_t* d_pairs = nullptr; uint64_t cap_pairs = 0;
-    uint32_t* d_result = nullptr; uint64_t cap_result = 0;
+    ck_buf<uint64_t> d_long;         // the list of long records (n_records entries)
+    // the staging of the host forms
+    ck_csr_buf in;
+    ck_buf<uint64_t> d_rows, d_rows_b;
+    ck_buf<uint32_t> d_counts, d_pairs, d_result;
 };
-
-void release_state(void* p)
-{
-    SketchState* S = (SketchState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_long, S->d_bytes, S->d_off, S->d_rows, S->d_counts, S->d_rows_b, S->d_pairs, S->d_result };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    ck_totals_release(&S->invalid);
-    delete S;
-}
 
 int state(circkit_ctx* c, SketchState** out)
 {
-    void** slot = ck_ctx_slot(c, CK_UNIT_SKETCH, release_state);
-    if (!*slot) *slot = new SketchState();
-    SketchState* S = (SketchState*)*slot;
-    *out = S;
+    SketchState* S = *out = ck_unit_state<SketchState>(c, CK_UNIT_SKETCH);
     int rc;
     if ((rc = ck_totals_make(c, &S->totals, T_WORDS))) return rc;
     return ck_totals_make(c, &S->invalid, 1);
-}
-
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
 }
 
 int check_params(circkit_ctx* c, const circkit_sketch_params* p)
@@ -121,7 +98,7 @@ int launch_sketch(circkit_ctx* c, SketchState* S, const uint8_t* d_bytes, const 
                   uint64_t* d_out, uint32_t* d_counts, uint32_t* d_anchors = nullptr)
 {
     int rc;
-    if ((rc = ck_grow(c, &S->d_long, &S->cap_long, n ? n : 1))) return rc;
+    if ((rc = S->d_long.grow(c, n))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if ((rc = ck_totals_clear(c, &S->totals, T_WORDS))) return rc;
     if (n) {
@@ -211,9 +188,9 @@ int circkit_sketch_batch_device(circkit_ctx* c, const uint8_t* d_bytes, const ui
     if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
     // the arrays whose extent the host knows; the payload's ends are the device's, and keeping the outputs off it is the caller's contract
     const uint64_t row_bytes = (n_records << params->log2_bins) * sizeof(uint64_t);
-    if (overlap(d_out_sketch, row_bytes, d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
-        overlap(d_out_n_kmers, n_records * sizeof(uint32_t), d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
-        overlap(d_out_sketch, row_bytes, d_out_n_kmers, n_records * sizeof(uint32_t)))
+    if (ck_overlap(d_out_sketch, row_bytes, d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
+        ck_overlap(d_out_n_kmers, n_records * sizeof(uint32_t), d_offsets, (n_records + 1) * sizeof(uint64_t)) ||
+        ck_overlap(d_out_sketch, row_bytes, d_out_n_kmers, n_records * sizeof(uint32_t)))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_sketch / d_out_n_kmers overlap the offsets or each other");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     SketchState* S;
@@ -233,9 +210,9 @@ int circkit_sketch_anchors_device(circkit_ctx* c, const uint8_t* d_bytes, const 
     if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
     const uint64_t row_bytes = (n_records << params->log2_bins) * sizeof(uint64_t), anchor_bytes = row_bytes / 2,
                    off_bytes = (n_records + 1) * sizeof(uint64_t), count_bytes = n_records * sizeof(uint32_t);
-    if (overlap(d_out_sketch, row_bytes, d_offsets, off_bytes) || overlap(d_out_n_kmers, count_bytes, d_offsets, off_bytes) ||
-        overlap(d_out_sketch, row_bytes, d_out_n_kmers, count_bytes) || overlap(d_out_anchors, anchor_bytes, d_offsets, off_bytes) ||
-        overlap(d_out_anchors, anchor_bytes, d_out_sketch, row_bytes) || overlap(d_out_anchors, anchor_bytes, d_out_n_kmers, count_bytes))
+    if (ck_overlap(d_out_sketch, row_bytes, d_offsets, off_bytes) || ck_overlap(d_out_n_kmers, count_bytes, d_offsets, off_bytes) ||
+        ck_overlap(d_out_sketch, row_bytes, d_out_n_kmers, count_bytes) || ck_overlap(d_out_anchors, anchor_bytes, d_offsets, off_bytes) ||
+        ck_overlap(d_out_anchors, anchor_bytes, d_out_sketch, row_bytes) || ck_overlap(d_out_anchors, anchor_bytes, d_out_n_kmers, count_bytes))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out_sketch / d_out_n_kmers / d_out_anchors overlap the offsets or each other");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     SketchState* S;
@@ -266,8 +243,8 @@ int circkit_sketch_compare_device(circkit_ctx* c, const uint64_t* d_sketch_a, ui
     if (((uintptr_t)d_sketch_a & 7u) || ((uintptr_t)d_sketch_b & 7u) || ((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_out & 3u))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "the sketches must be 8-byte aligned, d_pairs and d_out 4-byte aligned");
     const uint64_t out_bytes = n_pairs * 2 * sizeof(uint32_t);
-    if (overlap(d_out, out_bytes, d_pairs, out_bytes) || overlap(d_out, out_bytes, d_sketch_a, (n_a << log2_bins) * sizeof(uint64_t)) ||
-        overlap(d_out, out_bytes, d_sketch_b, (n_b << log2_bins) * sizeof(uint64_t)))
+    if (ck_overlap(d_out, out_bytes, d_pairs, out_bytes) || ck_overlap(d_out, out_bytes, d_sketch_a, (n_a << log2_bins) * sizeof(uint64_t)) ||
+        ck_overlap(d_out, out_bytes, d_sketch_b, (n_b << log2_bins) * sizeof(uint64_t)))
         return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "d_out overlaps the pairs or a sketch");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     SketchState* S;
@@ -297,28 +274,23 @@ int circkit_sketch_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* o
     if (n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_records too large");
     if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
     // from the offsets alone, before a payload byte is read
-    for (uint64_t i = 0; i < n_records; ++i) {
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] >= ck_sketch::TOO_LONG)
-            return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was sketched", (unsigned long long)i);
-    }
+    uint64_t at = 0;
+    const ck_csr_fault fault = ck_csr_walk(offsets, n_records, ck_sketch::TOO_LONG, &at);
+    if (fault == CK_CSR_DECREASE) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (fault) return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "record %llu has 2^31 symbols or more: nothing was sketched", (unsigned long long)at);
     const uint64_t nb = n_records ? offsets[n_records] : 0;
     if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     SketchState* S;
     if ((rc = state(c, &S))) return rc;
     const uint64_t n_rows = n_records << params->log2_bins;
-    if ((rc = ck_grow(c, &S->d_bytes, &S->cap_bytes, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, n_rows ? n_rows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_counts, &S->cap_counts, n_records ? n_records : 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
-    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = launch_sketch(c, S, S->d_bytes, S->d_off, n_records, *params, S->d_rows, S->d_counts))) return rc;
-    if (n_rows) CK_HIP(c, hipMemcpyAsync(out_sketch, S->d_rows, n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (n_records && out_n_kmers) CK_HIP(c, hipMemcpyAsync(out_n_kmers, S->d_counts, n_records * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
+    if ((rc = S->in.upload(c, bytes, offsets, n_records))) return rc;
+    if ((rc = S->d_rows.grow(c, n_rows))) return rc;
+    if ((rc = S->d_counts.grow(c, n_records))) return rc;
+    if ((rc = launch_sketch(c, S, S->in.bytes, S->in.off, n_records, *params, S->d_rows, S->d_counts))) return rc;
+    if ((rc = S->d_rows.download(c, out_sketch, n_rows))) return rc;
+    if ((rc = S->d_counts.download(c, out_n_kmers, n_records))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     return check_totals(c, S->totals.h);
 }
 
@@ -334,17 +306,14 @@ int circkit_sketch_compare(circkit_ctx* c, const uint64_t* sketch_a, uint64_t n_
     if ((rc = state(c, &S))) return rc;
     const bool same = sketch_a == sketch_b;
     const uint64_t wa = (same && n_b > n_a ? n_b : n_a) << log2_bins, wb = same ? 0 : n_b << log2_bins;
-    if ((rc = ck_grow(c, &S->d_rows, &S->cap_rows, wa ? wa : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_rows_b, &S->cap_rows_b, wb ? wb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_pairs, &S->cap_pairs, n_pairs ? 2 * n_pairs : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_result, &S->cap_result, n_pairs ? 2 * n_pairs : 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (n_pairs && wa) CK_HIP(c, hipMemcpyAsync(S->d_rows, sketch_a, wa * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_pairs && wb) CK_HIP(c, hipMemcpyAsync(S->d_rows_b, sketch_b, wb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_pairs) CK_HIP(c, hipMemcpyAsync(S->d_pairs, pairs, 2 * n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    // (without pairs no row is read: the sketches may be null then)
+    if ((rc = S->d_rows.upload(c, n_pairs ? sketch_a : nullptr, wa))) return rc;
+    if ((rc = S->d_rows_b.upload(c, n_pairs ? sketch_b : nullptr, wb))) return rc;
+    if ((rc = S->d_pairs.upload(c, pairs, 2 * n_pairs))) return rc;
+    if ((rc = S->d_result.grow(c, 2 * n_pairs))) return rc;
     if ((rc = launch_compare(c, S, S->d_rows, n_a, same ? S->d_rows : S->d_rows_b, n_b, log2_bins, S->d_pairs, n_pairs, S->d_result))) return rc;
-    if (n_pairs) CK_HIP(c, hipMemcpyAsync(out, S->d_result, 2 * n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
+    if ((rc = S->d_result.download(c, out, 2 * n_pairs))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     return check_invalid(c, S->invalid.h[0]);
 }
 

@@ -433,41 +433,27 @@ struct UniqWords {
 };
 
 struct UniqState {
-    UniqSlot* d_table = nullptr;         // [mask + 2]
+    ck_buf<UniqSlot> d_table;            // [mask + 2]
     uint64_t mask = 0, count = 0;        // slots - 1; upper bound of the keys folded in so far
     bool local = false;                  // the table holds circkit_uniq_resolve_device's split local values
     bool lost = false;                   // a rehash failed half-way: the stream's earlier batches are gone -- every uniq call fails until circkit_uniq_reset
-    UniqWords* d_words = nullptr;
-    // circkit_uniq_first_seen's staging (grow only): the batch's keys and their answers
-    uint64_t *d_keys = nullptr, *d_answers = nullptr;
-    uint64_t cap_keys = 0;
+    ck_buf<UniqWords> d_words;
+    // circkit_uniq_first_seen's staging: the batch's keys and their answers
+    ck_buf<uint64_t> d_keys, d_answers;
 };
-
-void release_state(void* p)
-{
-    UniqState* S = (UniqState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_table, S->d_words, S->d_keys, S->d_answers };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    delete S;
-}
 
 // Every entry point that touches the state starts here: sets the ctx's device and hands out its uniq state, made on first use
 // (the words zeroed on the ctx stream, in order with every later use of them).
 int uniq_state(circkit_ctx* c, UniqState** out)
 {
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
-    void** slot = ck_ctx_slot(c, CK_UNIT_UNIQ, release_state);
-    if (!*slot) {
-        UniqWords* w = nullptr;
-        CK_HIP(c, hipMalloc(&w, sizeof(UniqWords)));
-        const hipError_t e = hipMemsetAsync(w, 0, sizeof(UniqWords), ck_ctx_stream(c));
-        if (e != hipSuccess) { (void)hipFree(w); return ck_fail(c, CIRCKIT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e)); }
-        UniqState* S = new UniqState();
-        S->d_words = w;
-        *slot = S;
+    UniqState* S = *out = ck_unit_state<UniqState>(c, CK_UNIT_UNIQ);
+    if (!S->d_words) {
+        const int rc = S->d_words.grow(c, 1);
+        if (rc) return rc;
+        const hipError_t e = hipMemsetAsync(S->d_words, 0, sizeof(UniqWords), ck_ctx_stream(c));
+        if (e != hipSuccess) { S->d_words.release(); return ck_fail(c, CIRCKIT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e)); }
     }
-    *out = (UniqState*)*slot;
     return CIRCKIT_OK;
 }
 
@@ -481,14 +467,6 @@ int uniq_table_ready(circkit_ctx* c, UniqState** out)
     return CIRCKIT_OK;
 }
 
-template <class T>
-int grow(circkit_ctx* c, T*& p, uint64_t want_elems)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
-    CK_HIP(c, hipMalloc(&p, want_elems * sizeof(T)));
-    return CIRCKIT_OK;
-}
-
 // the table sized (allocated) for `expected_keys` distinct keys at CK_UNIQ_LOAD_PCT; contents untouched
 int uniq_size(circkit_ctx* c, UniqState* S, uint64_t expected_keys)
 {
@@ -496,8 +474,9 @@ int uniq_size(circkit_ctx* c, UniqState* S, uint64_t expected_keys)
     while (cap * CK_UNIQ_LOAD_PCT < expected_keys * 100) cap <<= 1;
     if (cap - 1 != S->mask || !S->d_table) {
         S->mask = 0;
+        S->d_table.release();            // another size, not only a larger one
         int rc;
-        if ((rc = grow(c, S->d_table, cap + 1))) return rc;
+        if ((rc = S->d_table.grow(c, cap + 1))) return rc;
         S->mask = cap - 1;
     }
     return CIRCKIT_OK;
@@ -556,7 +535,7 @@ int circkit_uniq_first_seen(circkit_ctx* c, const uint64_t* hash, uint64_t n, ui
             hipLaunchKernelGGL(uniq_rehash_kernel, dim3(N_CU * 8), dim3(256), 0, st, (const UniqSlot*)S->d_table, S->mask + 2, nt, cap - 1);
             hipError_t e = hipStreamSynchronize(st);
             if (e == hipSuccess && getenv("CIRCKIT_TEST_FAIL_REHASH")) e = hipErrorUnknown;      // fault injection (tests/test_gpu_parity.py)
-            (void)hipFree(S->d_table); S->d_table = nullptr;
+            S->d_table.release();
             if (e != hipSuccess) {
                 // the old table is gone and the new one holds who knows what: not a state to go on from silently -- every
                 // later call fails until the caller starts over with circkit_uniq_reset
@@ -567,14 +546,12 @@ int circkit_uniq_first_seen(circkit_ctx* c, const uint64_t* hash, uint64_t n, ui
         } else {
             CK_HIP(c, hipMemsetAsync(&S->d_words->overflow, 0, 4, st));
         }
-        S->d_table = nt; S->mask = cap - 1;
+        S->d_table.adopt(nt, cap + 1); S->mask = cap - 1;
     }
-    if (n > S->cap_keys) {
+    if (n > S->d_keys.cap || n > S->d_answers.cap) {
         const uint64_t nk = n + n / 8 + 1024;
-        S->cap_keys = 0;
-        if ((rc = grow(c, S->d_keys, nk))) return rc;
-        if ((rc = grow(c, S->d_answers, nk))) return rc;
-        S->cap_keys = nk;
+        if ((rc = S->d_keys.grow(c, nk))) return rc;
+        if ((rc = S->d_answers.grow(c, nk))) return rc;
     }
     CK_HIP(c, hipMemcpyAsync(S->d_keys, hash, n * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(uniq_insert_kernel, dim3(UNIQ_GRID), dim3(256), 0, st, (const uint64_t*)S->d_keys, (const uint64_t*)nullptr, n, base_index,
@@ -713,7 +690,7 @@ int circkit_uniq_resolve_device(circkit_ctx* c, const uint64_t* d_hash, uint64_t
         while (log2b < BKT_MAX_LOG2 && ((uint64_t)CK_BKT_KEYS << log2b) < n) ++log2b;
         const uint32_t B = 1u << log2b;
         const uint64_t per = (n + BKT_NW - 1) / BKT_NW;
-        uint8_t* scratch = reinterpret_cast<uint8_t*>(S->d_table);
+        uint8_t* scratch = reinterpret_cast<uint8_t*>(S->d_table.p);
         uint64_t* rows = reinterpret_cast<uint64_t*>(scratch);
         uint32_t* counts = reinterpret_cast<uint32_t*>(scratch + ((n * 16 + 255) & ~255ull));
         uint32_t* tot = counts + (uint64_t)BKT_NW * B;

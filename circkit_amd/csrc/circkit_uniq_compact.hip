@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "ck_compact_launch.h"
 #include "monomer_compact.h"
@@ -32,33 +33,13 @@ __global__ __launch_bounds__(DECIDE_WG) void uniq_compact_decide_kernel(const ui
 
 struct UniqCompactState {
     ck_totals totals;                    // [CK_COMPACT_WORDS], of the most recent uniq compact of this ctx
-    // circkit_uniq_batch's staging (grow only)
-    uint8_t* d_in = nullptr; uint64_t cap_in = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    uint8_t* d_canon = nullptr; uint64_t cap_canon = 0;
-    uint64_t* d_hash = nullptr; uint64_t cap_hash = 0;
-    uint64_t* d_fs = nullptr; uint64_t cap_fs = 0;
-    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
-    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
-    uint64_t* d_out_src = nullptr; uint64_t cap_out_src = 0;
+    // circkit_uniq_batch's staging
+    ck_csr_buf in;
+    ck_buf<uint8_t> d_canon, d_out;
+    ck_buf<uint64_t> d_hash, d_fs, d_out_off, d_out_src;
 };
 
-void release_state(void* p)
-{
-    UniqCompactState* S = (UniqCompactState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_in, S->d_off, S->d_canon, S->d_hash, S->d_fs, S->d_out, S->d_out_off, S->d_out_src };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->totals);
-    delete S;
-}
-
-UniqCompactState* state(circkit_ctx* c)
-{
-    void** slot = ck_ctx_slot(c, CK_UNIT_UNIQ_COMPACT, release_state);
-    if (!*slot) *slot = new UniqCompactState();
-    return (UniqCompactState*)*slot;
-}
+UniqCompactState* state(circkit_ctx* c) { return ck_unit_state<UniqCompactState>(c, CK_UNIT_UNIQ_COMPACT); }
 
 // the decide kernel and the shared kernels behind it, on the ctx stream; nothing waits
 int launch(circkit_ctx* c, UniqCompactState* S, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_first_seen,
@@ -118,8 +99,8 @@ int circkit_uniq_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     if (n >= 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "circkit_uniq_batch: n_records must be < 2^32 - 1");
     if (n && (!out_src || (offsets[n] > offsets[0] && (!bytes || !out_bytes)))) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
     if (offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    uint64_t at = 0;
+    if (ck_csr_walk(offsets, n, CK_CSR_NO_LIMIT, &at)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
     UniqCompactState* S = state(c);
     if (n_kept) *n_kept = 0;
@@ -131,21 +112,17 @@ int circkit_uniq_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         return CIRCKIT_OK;
     }
     const uint64_t nb = offsets[n];
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n + 1))) return rc;
-    if (canonical_out && (rc = ck_grow(c, &S->d_canon, &S->cap_canon, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_hash, &S->cap_hash, n))) return rc;
-    if ((rc = ck_grow(c, &S->d_fs, &S->cap_fs, n))) return rc;
-    if ((rc = ck_grow(c, &S->d_out, &S->cap_out, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_src, &S->cap_out_src, n))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = circkit_canonicalize_batch_device(c, S->d_in, S->d_off, n, canonical_out ? S->d_canon : nullptr, nullptr, nullptr, S->d_hash)))
-        return rc;
+    if ((rc = S->in.upload(c, bytes, offsets, n))) return rc;
+    if (canonical_out && (rc = S->d_canon.grow(c, nb))) return rc;
+    if ((rc = S->d_hash.grow(c, n))) return rc;
+    if ((rc = S->d_fs.grow(c, n))) return rc;
+    if ((rc = S->d_out.grow(c, nb))) return rc;
+    if ((rc = S->d_out_off.grow(c, n + 1))) return rc;
+    if ((rc = S->d_out_src.grow(c, n))) return rc;
+    uint8_t* const d_canon = canonical_out ? S->d_canon.p : nullptr;
+    if ((rc = circkit_canonicalize_batch_device(c, S->in.bytes, S->in.off, n, d_canon, nullptr, nullptr, S->d_hash))) return rc;
     if ((rc = circkit_uniq_resolve_device(c, S->d_hash, n, 0, S->d_fs, nullptr))) return rc;
-    if ((rc = launch(c, S, canonical_out ? S->d_canon : S->d_in, S->d_off, n, S->d_fs, 0, S->d_out, S->d_out_off, S->d_out_src, nullptr, nullptr)))
+    if ((rc = launch(c, S, d_canon ? d_canon : S->in.bytes.p, S->in.off, n, S->d_fs, 0, S->d_out, S->d_out_off, S->d_out_src, nullptr, nullptr)))
         return rc;
     // three waits on a stream that has run dry after the first: a record the canonicalize left alone, keys that found no slot
     uint32_t unprocessed = 0;
@@ -153,11 +130,11 @@ int circkit_uniq_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     if ((rc = circkit_uniq_status(c, nullptr))) return rc;
     if ((rc = check_totals(c, S->totals.h))) return rc;
     const uint64_t m = S->totals.h[CK_COMPACT_RECORDS], B = S->totals.h[CK_COMPACT_BYTES];
-    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (m) CK_HIP(c, hipMemcpyAsync(out_src, S->d_out_src, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (first_seen) CK_HIP(c, hipMemcpyAsync(first_seen, S->d_fs, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (B) CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
+    if ((rc = S->d_out_off.download(c, out_offsets, m + 1))) return rc;
+    if ((rc = S->d_out_src.download(c, out_src, m))) return rc;
+    if ((rc = S->d_fs.download(c, first_seen, n))) return rc;
+    if ((rc = S->d_out.download(c, out_bytes, B))) return rc;
+    CK_HIP(c, hipStreamSynchronize(ck_ctx_stream(c)));
     if (n_kept) *n_kept = m;
     return CIRCKIT_OK;
 }

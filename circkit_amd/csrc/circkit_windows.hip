@@ -22,6 +22,7 @@
 #include <stdio.h>
 
 #include "../../include/circkit.h"
+#include "ck_csr.h"
 #include "ck_ctx.h"
 #include "ck_scan.h"
 #include "window_gather.h"
@@ -192,38 +193,15 @@ struct Totals : ck_totals {          // [T_WORDS], made at the first call of the
 
 struct WindowsState {
     Totals gather, translate;
-    uint64_t* d_sums = nullptr; uint64_t cap_sums = 0;
-    // the staging of circkit_windows_gather and circkit_windows_translate (grow only)
-    uint8_t* d_in = nullptr; uint64_t cap_in = 0;
-    uint64_t* d_off = nullptr; uint64_t cap_off = 0;
-    Window* d_win = nullptr; uint64_t cap_win = 0;
-    uint64_t* d_out_off = nullptr; uint64_t cap_out_off = 0;
-    uint8_t* d_out = nullptr; uint64_t cap_out = 0;
+    ck_buf<uint64_t> d_sums;
+    // the staging of circkit_windows_gather and circkit_windows_translate
+    ck_csr_buf in;
+    ck_buf<Window> d_win;
+    ck_buf<uint64_t> d_out_off;
+    ck_buf<uint8_t> d_out;
 };
 
-void release_state(void* p)
-{
-    WindowsState* S = (WindowsState*)p;
-    if (!S) return;
-    void* ptrs[] = { S->d_sums, S->d_in, S->d_off, S->d_win, S->d_out_off, S->d_out };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    ck_totals_release(&S->gather);
-    ck_totals_release(&S->translate);
-    delete S;
-}
-
-WindowsState* state(circkit_ctx* c)
-{
-    void** slot = ck_ctx_slot(c, CK_UNIT_WINDOWS, release_state);
-    if (!*slot) *slot = new WindowsState();
-    return (WindowsState*)*slot;
-}
-
-uint32_t lane_grid(uint64_t items)
-{
-    const uint64_t grid = (items + WIN_WG - 1) / WIN_WG;
-    return (uint32_t)(grid > WIN_MAX_GRID ? WIN_MAX_GRID : grid);
-}
+WindowsState* state(circkit_ctx* c) { return ck_unit_state<WindowsState>(c, CK_UNIT_WINDOWS); }
 
 // lengths (in bytes, or in residues for a translate), the scan with its refusals, and the copy of the totals: out_offsets is
 // complete and R->h valid once the stream has run past it.  d_out is only compared with the payload.
@@ -233,14 +211,14 @@ int launch_offsets(circkit_ctx* c, WindowsState* S, Totals* R, bool residues, co
     int rc;
     if ((rc = ck_totals_make(c, R, T_WORDS))) return rc;
     const uint64_t tiles = (m + WSCAN_TILE - 1) / WSCAN_TILE;
-    if ((rc = ck_grow(c, &S->d_sums, &S->cap_sums, tiles ? tiles : 1))) return rc;
+    if ((rc = S->d_sums.grow(c, tiles))) return rc;
     hipStream_t st = ck_ctx_stream(c);
     if ((rc = ck_totals_clear(c, R, T_WORDS))) return rc;
     if (m) {
         if (residues)
-            hipLaunchKernelGGL(windows_residues_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
+            hipLaunchKernelGGL(windows_residues_kernel, dim3(ck_grid_of(m, WIN_WG, WIN_MAX_GRID)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
         else
-            hipLaunchKernelGGL(windows_lengths_kernel, dim3(lane_grid(m)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
+            hipLaunchKernelGGL(windows_lengths_kernel, dim3(ck_grid_of(m, WIN_WG, WIN_MAX_GRID)), dim3(WIN_WG), 0, st, d_offsets, n_records, d_windows, m, d_out_offsets, R->d);
         hipLaunchKernelGGL(windows_tile_sums_kernel, dim3((uint32_t)tiles), dim3(WSCAN_WG), 0, st, (const uint64_t*)d_out_offsets + 1, m, S->d_sums);
     }
     hipLaunchKernelGGL(windows_scan_sums_kernel, dim3(1), dim3(WSCAN_WG), 0, st, S->d_sums, tiles, d_bytes, d_offsets, m ? n_records : 0, d_out, capacity,
@@ -302,6 +280,45 @@ int check_translate_params(circkit_ctx* c, const circkit_translate_params* p)
     return CIRCKIT_OK;
 }
 
+// The host form of a gather or a translate: the batch and the windows staged, the offsets first (the staging for the output is
+// sized by the total they end in, so it cannot overlap the staged payload), then `launch` into that staging.  The totals
+// (`kind`), `residues`, `launch` and `verdict` are the kind's own.
+template <class Launch>
+int host_form(circkit_ctx* c, Totals WindowsState::*kind, bool residues, const uint8_t* bytes, const uint64_t* offsets, uint64_t n_records,
+              const circkit_window* windows, uint64_t n_windows, uint8_t* out, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total,
+              const Launch& launch, int (*verdict)(circkit_ctx*, const uint64_t*, uint64_t))
+{
+    if (!out_offsets || (n_records && !offsets) || (n_windows && !windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
+    uint64_t at = 0;
+    if (ck_csr_walk(offsets, n_records, CK_CSR_NO_LIMIT, &at)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
+    if (n_records && offsets[n_records] && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
+    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
+    WindowsState* S = state(c);
+    Totals* R = &(S->*kind);
+    int rc;
+    if ((rc = S->in.upload(c, bytes, offsets, n_records))) return rc;
+    if ((rc = S->d_win.upload(c, (const Window*)windows, n_windows))) return rc;
+    if ((rc = S->d_out_off.grow(c, n_windows + 1))) return rc;
+    if ((rc = launch_offsets(c, S, R, residues, S->in.bytes, S->in.off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
+    if ((rc = ck_totals_fetch(c, R, T_WORDS))) return rc;
+    if ((rc = S->d_out_off.download(c, out_offsets, n_windows + 1))) return rc;
+    hipStream_t st = ck_ctx_stream(c);
+    CK_HIP(c, hipStreamSynchronize(st));
+    const uint64_t B = R->h[T_TOTAL];
+    if (total) *total = B;
+    if (R->h[T_REFUSED]) return verdict(c, R->h, out_capacity);
+    if (B) {
+        if (!out) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
+        if ((rc = S->d_out.grow(c, B))) return rc;
+        if ((rc = launch(S, S->d_out.p))) return rc;
+        if ((rc = S->d_out.download(c, out, B))) return rc;
+        CK_HIP(c, hipStreamSynchronize(st));
+    }
+    return verdict(c, R->h, out_capacity);
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,7 +364,7 @@ int circkit_windows_of_records_device(circkit_ctx* c, const uint64_t* d_offsets,
     if (n_records > 0xFFFFFFFFull) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "a window names its record in 32 bits: n_records must be <= 2^32 - 1");
     if (!n_records) return CIRCKIT_OK;
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
-    hipLaunchKernelGGL(windows_of_records_kernel, dim3(lane_grid(n_records)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_offsets, n_records, kind, bases, percent,
+    hipLaunchKernelGGL(windows_of_records_kernel, dim3(ck_grid_of(n_records, WIN_WG, WIN_MAX_GRID)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_offsets, n_records, kind, bases, percent,
                        (Window*)d_windows);
     CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
@@ -362,7 +379,7 @@ int circkit_orfs_windows_device(circkit_ctx* c, const uint64_t* d_orf_offsets, c
     if (n_orfs >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_orfs too large");
     if (!n_orfs) return CIRCKIT_OK;
     CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
-    hipLaunchKernelGGL(orfs_windows_kernel, dim3(lane_grid(n_orfs)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_orf_offsets, d_orfs, n_records, n_orfs,
+    hipLaunchKernelGGL(orfs_windows_kernel, dim3(ck_grid_of(n_orfs, WIN_WG, WIN_MAX_GRID)), dim3(WIN_WG), 0, ck_ctx_stream(c), d_orf_offsets, d_orfs, n_records, n_orfs,
                        include_stop ? 0u : 3u, (Window*)d_windows);
     CK_HIP(c, hipGetLastError());
     return CIRCKIT_OK;
@@ -372,40 +389,9 @@ int circkit_windows_gather(circkit_ctx* c, const uint8_t* bytes, const uint64_t*
                            uint64_t n_windows, uint8_t* out_bytes, uint64_t out_capacity, uint64_t* out_offsets, uint64_t* total)
 {
     if (!c) return CIRCKIT_ERR_INVALID_ARG;
-    if (!out_offsets || (n_records && !offsets) || (n_windows && !windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-    const uint64_t nb = n_records ? offsets[n_records] : 0;
-    if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
-    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
-    WindowsState* S = state(c);
-    int rc;
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
-    // the offsets first: the staging for the bytes is sized by the total they end in (it cannot overlap the staged payload)
-    if ((rc = launch_offsets(c, S, &S->gather, false, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = ck_totals_fetch(c, &S->gather, T_WORDS))) return rc;
-    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
-    const uint64_t B = S->gather.h[T_TOTAL];
-    if (total) *total = B;
-    if (S->gather.h[T_REFUSED]) return check_totals(c, S->gather.h, out_capacity);
-    if (B) {
-        if (!out_bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
-        if ((rc = launch_gather(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, S->d_out_off, S->d_out))) return rc;
-        CK_HIP(c, hipMemcpyAsync(out_bytes, S->d_out, B, hipMemcpyDeviceToHost, st));
-        CK_HIP(c, hipStreamSynchronize(st));
-    }
-    return check_totals(c, S->gather.h, out_capacity);
+    return host_form(c, &WindowsState::gather, false, bytes, offsets, n_records, windows, n_windows, out_bytes, out_capacity, out_offsets, total,
+                     [&](WindowsState* S, uint8_t* d_out) { return launch_gather(c, S, S->in.bytes, S->in.off, n_records, S->d_win, n_windows, S->d_out_off, d_out); },
+                     check_totals);
 }
 
 int circkit_windows_translate_device(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n_records,
@@ -446,40 +432,11 @@ int circkit_windows_translate(circkit_ctx* c, const uint8_t* bytes, const uint64
     if (!c) return CIRCKIT_ERR_INVALID_ARG;
     int rc;
     if ((rc = check_translate_params(c, params))) return rc;
-    if (!out_offsets || (n_records && !offsets) || (n_windows && !windows)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-    if (n_records && offsets[0] != 0) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets[0] must be 0");
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (offsets[i + 1] < offsets[i]) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "offsets must not decrease");
-    const uint64_t nb = n_records ? offsets[n_records] : 0;
-    if (nb && !bytes) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-    if (n_windows >= (1ull << 40) || n_records >= (1ull << 40)) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "n_windows or n_records too large");
-    CK_HIP(c, hipSetDevice(ck_ctx_device(c)));
-    WindowsState* S = state(c);
-    Totals* R = &S->translate;
-    if ((rc = ck_grow(c, &S->d_in, &S->cap_in, nb ? nb : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_off, &S->cap_off, n_records + 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_win, &S->cap_win, n_windows ? n_windows : 1))) return rc;
-    if ((rc = ck_grow(c, &S->d_out_off, &S->cap_out_off, n_windows + 1))) return rc;
-    hipStream_t st = ck_ctx_stream(c);
-    if (nb) CK_HIP(c, hipMemcpyAsync(S->d_in, bytes, nb, hipMemcpyHostToDevice, st));
-    if (n_records) CK_HIP(c, hipMemcpyAsync(S->d_off, offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (n_windows) CK_HIP(c, hipMemcpyAsync(S->d_win, windows, n_windows * sizeof(Window), hipMemcpyHostToDevice, st));
-    // the offsets first: the staging for the residues is sized by the total they end in (it cannot overlap the staged payload)
-    if ((rc = launch_offsets(c, S, R, true, S->d_in, S->d_off, n_records, S->d_win, n_windows, nullptr, out_capacity, S->d_out_off))) return rc;
-    if ((rc = ck_totals_fetch(c, R, T_WORDS))) return rc;
-    CK_HIP(c, hipMemcpyAsync(out_offsets, S->d_out_off, (n_windows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CK_HIP(c, hipStreamSynchronize(st));
-    const uint64_t B = R->h[T_TOTAL];
-    if (total) *total = B;
-    if (R->h[T_REFUSED]) return check_translate_totals(c, R->h, out_capacity);
-    if (B) {
-        if (!out_aa) return ck_ctx_fail(c, CIRCKIT_ERR_INVALID_ARG, "null buffer");
-        if ((rc = ck_grow(c, &S->d_out, &S->cap_out, B))) return rc;
-        if ((rc = launch_translate(c, S, S->d_in, S->d_off, n_records, S->d_win, n_windows, *params, S->d_out_off, S->d_out))) return rc;
-        CK_HIP(c, hipMemcpyAsync(out_aa, S->d_out, B, hipMemcpyDeviceToHost, st));
-        CK_HIP(c, hipStreamSynchronize(st));
-    }
-    return check_translate_totals(c, R->h, out_capacity);
+    return host_form(c, &WindowsState::translate, true, bytes, offsets, n_records, windows, n_windows, out_aa, out_capacity, out_offsets, total,
+                     [&](WindowsState* S, uint8_t* d_out) {
+                         return launch_translate(c, S, S->in.bytes, S->in.off, n_records, S->d_win, n_windows, *params, S->d_out_off, d_out);
+                     },
+                     check_translate_totals);
 }
 
 }  // extern "C"

@@ -3,8 +3,9 @@
 // struct circkit_ctx is defined in ck_ctx_impl.h, which only circkit_hip.hip (the ctx's lifecycle) and circkit_canon.hip (the
 // canonicalize state, allocated with the ctx) include; nothing else names one of its fields.  The other units (one
 // circkit_*.hip per ck_unit below, and circkit_bench.hip) enqueue on the ctx's stream, report through its error string and keep their own state behind
-// one slot each, which circkit_ctx_destroy releases.  What that state is made of is here once: a grow-only device buffer
-// (ck_grow) and the totals of a unit's most recent call (ck_totals).
+// one slot each, which circkit_ctx_destroy releases.  What that state is made of is here once: a grow-only device buffer that
+// frees itself and stages host arrays (ck_buf, ck_csr_buf), the totals of a unit's most recent call (ck_totals), the typed
+// slot (ck_unit_state), and the two small helpers the units share (ck_overlap, ck_grid_of).  The walk over a host batch's offsets is ck_csr.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,15 +38,80 @@ void** ck_ctx_slot(circkit_ctx* c, ck_unit unit, void (*release)(void*));
 // stream, so that its status answers for its own resolve whatever uses the table afterwards.  *out stays valid for the ctx's life.
 int ck_uniq_overflow_word(circkit_ctx* c, const uint32_t** out);
 
-// A device buffer of a unit's state that only grows: *p holds at least `want` elements afterwards (its contents are not kept).
+// A device buffer that only grows, and its capacity: what a unit's state (and the ctx's own) is made of.  It frees itself, so a
+// state struct lists its buffers once, as members.  Reads as the pointer it holds.
 template <typename T>
-int ck_grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
+struct ck_buf {
+    T* p = nullptr;
+    uint64_t cap = 0;                // elements
+    ck_buf() = default;
+    ck_buf(const ck_buf&) = delete;
+    ck_buf& operator=(const ck_buf&) = delete;
+    ~ck_buf() { release(); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // frees what it holds and owns q[n] instead
+    void adopt(T* q, uint64_t n) { release(); p = q; cap = n; }
+    // at least `want` elements afterwards, and never none (its contents are not kept)
+    int grow(circkit_ctx* c, uint64_t want)
+    {
+        if (!want) want = 1;
+        if (want <= cap) return CIRCKIT_OK;
+        release();
+        CK_HIP(c, hipMalloc((void**)&p, want * sizeof(T)));
+        cap = want;
+        return CIRCKIT_OK;
+    }
+    // grown for n elements, then src[n] copied in on the ctx stream (nothing is copied from a null src)
+    int upload(circkit_ctx* c, const T* src, uint64_t n)
+    {
+        const int rc = grow(c, n);
+        if (rc) return rc;
+        if (n && src) CK_HIP(c, hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, ck_ctx_stream(c)));
+        return CIRCKIT_OK;
+    }
+    // its first n elements copied to dst on the ctx stream (nothing to a null dst)
+    int download(circkit_ctx* c, T* dst, uint64_t n) const
+    {
+        if (n && dst) CK_HIP(c, hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
+        return CIRCKIT_OK;
+    }
+};
+
+// The staging of a host CSR batch: the payload and the n + 1 offsets, which the caller has checked (ck_csr.h).
+struct ck_csr_buf {
+    ck_buf<uint8_t> bytes;
+    ck_buf<uint64_t> off;
+    int upload(circkit_ctx* c, const uint8_t* src_bytes, const uint64_t* src_offsets, uint64_t n_records)
+    {
+        const int rc = bytes.upload(c, src_bytes, n_records ? src_offsets[n_records] : 0);
+        if (rc) return rc;
+        return n_records ? off.upload(c, src_offsets, n_records + 1) : off.grow(c, 1);
+    }
+};
+
+// A unit's state in its slot: made on first use, deleted by circkit_ctx_destroy -- S's destructor is the only place that frees.
+template <class S>
+S* ck_unit_state(circkit_ctx* c, ck_unit unit)
 {
-    if (want <= *cap) return CIRCKIT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    CK_HIP(c, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return CIRCKIT_OK;
+    void** slot = ck_ctx_slot(c, unit, [](void* p) { delete static_cast<S*>(p); });
+    if (!*slot) *slot = new S();
+    return static_cast<S*>(*slot);
+}
+
+// [a, a + na) and [b, b + nb) share a byte (neither null nor empty)
+inline bool ck_overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+// the workgroups that take `work` items `per_block` at a time, at most max_grid of them (the kernel strides beyond)
+inline uint32_t ck_grid_of(uint64_t work, uint32_t per_block, uint32_t max_grid)
+{
+    const uint64_t blocks = (work + per_block - 1) / per_block;
+    return (uint32_t)(blocks > max_grid ? max_grid : blocks);
 }
 
 // The totals of a unit's most recent call: a few 64-bit words that the kernels write in device memory, and the same words in
@@ -53,6 +119,14 @@ int ck_grow(circkit_ctx* c, T** p, uint64_t* cap, uint64_t want)
 struct ck_totals {
     uint64_t* d = nullptr;
     uint64_t* h = nullptr;
+    ck_totals() = default;
+    ck_totals(const ck_totals&) = delete;
+    ck_totals& operator=(const ck_totals&) = delete;
+    ~ck_totals()
+    {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+    }
 };
 // both where missing; new host words are 0
 inline int ck_totals_make(circkit_ctx* c, ck_totals* T, int words)
@@ -74,10 +148,4 @@ inline int ck_totals_fetch(circkit_ctx* c, ck_totals* T, int words)
 {
     CK_HIP(c, hipMemcpyAsync(T->h, T->d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ck_ctx_stream(c)));
     return CIRCKIT_OK;
-}
-inline void ck_totals_release(ck_totals* T)
-{
-    if (T->d) (void)hipFree(T->d);
-    if (T->h) (void)hipHostFree(T->h);
-    T->d = T->h = nullptr;
 }

@@ -33,11 +33,11 @@ struct circkit_ctx {
     uint8_t *d_in = nullptr, *d_out = nullptr, *d_strand = nullptr;
     uint64_t* d_off = nullptr; uint32_t* d_idx = nullptr; uint64_t* d_hash = nullptr;
     uint64_t cap_bytes = 0, cap_rec = 0;
-    uint32_t* d_view = nullptr; uint64_t cap_view = 0;        // hash-only batches: strand + rotation of the records whose hash is not fused
-    uint8_t* d_hashed = nullptr; uint64_t cap_hashed = 0;     // per record: hash already written by the streaming kernel
+    ck_buf<uint32_t> d_view;             // hash-only batches: strand + rotation of the records whose hash is not fused
+    ck_buf<uint8_t> d_hashed;            // per record: hash already written by the streaming kernel
     // records beyond the last LDS tier run the same per-record code over slices of this global-memory scratch
     // (grow-only; the device API allocates the default on first use, the host API sizes it for the batch's longest record)
-    uint32_t* d_gscratch = nullptr; uint64_t cap_gscratch = 0;    // bytes
+    ck_buf<uint8_t> d_gscratch;          // (its capacity in bytes; the kernels take it as words)
     uint64_t gscratch_default = 256ull << 20;
     // the previous batch's mode (1 / 2 / 3, see stream_mode): only picks which build gets the full-size grid
     uint64_t* h_off = nullptr;           // page-locked staging of a host batch's offsets and per-record outputs (host_batch): h_off_cap x (8 + 8 + 4 + 1) bytes
@@ -45,6 +45,6 @@ struct circkit_ctx {
     volatile uint32_t* h_mode = nullptr; // pinned host word the rescue kernel writes the batch's mode to (d_mode = its device address)
     uint32_t* d_mode = nullptr;
     uint32_t mode_seen = 0;                   // launch_canon: the mode word as the previous device batch's launch read it (MODE_GUESS)
-    // the other units' state (ck_ctx.h): each puts its buffers in its slot and names the function that frees them
+    // the other units' state (ck_ctx.h): each puts its state in its slot and names the function that deletes it
     struct { void* p; void (*release)(void*); } units[CK_N_UNITS] = {};
 };
