@@ -39,11 +39,11 @@ def constants():
     return int(out[0]), int(out[1])
 
 
-def _run(blob, tmp_dir, timeout):
+def _run(blob, tmp_dir, timeout, schedule=None):
     src, dst = os.path.join(str(tmp_dir), "cluster_cases.bin"), os.path.join(str(tmp_dir), "cluster_results.bin")
     with open(src, "wb") as f:
         f.write(blob)
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "cluster_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     return open(dst, "rb").read()
 
@@ -52,14 +52,14 @@ def _u64(values):
     return np.array([int(v) for v in values], dtype=np.uint64).tobytes()
 
 
-def run_candidates(cases, tmp_dir, timeout=900):
+def run_candidates(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(rows (n, bins), n_bands, band_bins, capacity, keys_waves, emit_waves)].  Returns per case (keys (n, n_bands),
     offsets, pair buffer (capacity, 2) with UNWRITTEN where nothing was written, total)."""
     blob = [_u64([len(cases)])]
     for rows, n_bands, band_bins, capacity, keys_waves, emit_waves in cases:
         rows = np.ascontiguousarray(rows, dtype=np.uint64)
         blob += [_u64([0, len(rows), rows.shape[1].bit_length() - 1, n_bands, band_bins, capacity, keys_waves, emit_waves]), rows.tobytes()]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for k, (rows, n_bands, _, capacity, _, _) in enumerate(cases):
         rc, total = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=2, offset=at))
@@ -77,7 +77,7 @@ def run_candidates(cases, tmp_dir, timeout=900):
     return out
 
 
-def run_link(cases, tmp_dir, timeout=900):
+def run_link(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(n, pairs (m, 2), scores (m, 2), (min_similarity_q16, min_filled), link_waves, flatten_waves)].  Returns per case
     (labels, clusters, linked, invalid)."""
     blob = [_u64([len(cases)])]
@@ -86,7 +86,7 @@ def run_link(cases, tmp_dir, timeout=900):
         scores = np.ascontiguousarray(scores, dtype=np.uint32).reshape(-1, 2)
         assert len(pairs) == len(scores)
         blob += [_u64([1, n, len(pairs), q16, min_filled, link_waves, flatten_waves]), pairs.tobytes(), scores.tobytes()]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for k, case in enumerate(cases):
         rc, clusters, linked, invalid = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=4, offset=at))

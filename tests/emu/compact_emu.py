@@ -56,7 +56,7 @@ def waves():
 
 
 def compact(data, offsets, ends, full_len=None, in_shift=0, out_shift=0, lead=0, min_length=0, max_length=None, min_overlap=None,
-            min_overlap_percent=None, keep_all=False):
+            min_overlap_percent=None, keep_all=False, schedule=None):
     """decide + scan + the gather's workgroup body on a CSR batch: (out_data, out_offsets, out_src, kept_end).
     in_shift / out_shift: the payload / output pointer mod 16; lead: offsets[0] (canary bytes in front of the first record).
     Canaries surround the payload and every output; the input is checked to be unchanged.  A lead of HIGH_LEAD bytes and more
@@ -90,11 +90,12 @@ def compact(data, offsets, ends, full_len=None, in_shift=0, out_shift=0, lead=0,
     kept = np.full(64 + n + 64, END_CANARY, dtype=np.uint32)
     fl = np.ascontiguousarray(full_len, dtype=np.uint64) if full_len is not None else None
     m = ctypes.c_uint64(0)
-    rc = L.emu_monomers_compact(pad.ctypes.data, offsets.ctypes.data, n, ends.ctypes.data, fl.ctypes.data if fl is not None else None,
-                                int(min_length), 2 ** 64 - 1 if max_length is None else int(max_length), int(min_overlap or 0),
-                                float(min_overlap_percent) if min_overlap_percent is not None else 0.0, int(min_overlap_percent is not None),
-                                int(bool(keep_all)), out.ctypes.data, out_off[64:].ctypes.data, out_src[64:].ctypes.data,
-                                kept[64:].ctypes.data, ctypes.byref(m))
+    with emu.scheduled(schedule):
+        rc = L.emu_monomers_compact(pad.ctypes.data, offsets.ctypes.data, n, ends.ctypes.data, fl.ctypes.data if fl is not None else None,
+                                    int(min_length), 2 ** 64 - 1 if max_length is None else int(max_length), int(min_overlap or 0),
+                                    float(min_overlap_percent) if min_overlap_percent is not None else 0.0, int(min_overlap_percent is not None),
+                                    int(bool(keep_all)), out.ctypes.data, out_off[64:].ctypes.data, out_src[64:].ctypes.data,
+                                    kept[64:].ctypes.data, ctypes.byref(m))
     assert rc == 0, "the lanes of a wave disagree on the record their search found"
     m = m.value
     assert np.array_equal(window, before), "the compact wrote into its input"

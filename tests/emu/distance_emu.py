@@ -39,7 +39,7 @@ def _u64(values):
     return np.array([int(v) for v in values], dtype=np.uint64).tobytes()
 
 
-def run(cases, tmp_dir, waves=3, timeout=900):
+def run(cases, tmp_dir, waves=3, timeout=900, schedule=None):
     """cases: tests/distance_sets.py's Case objects.  Returns per case (distance or None, scores or None, within, invalid)."""
     blob = [_u64([len(cases)])]
     for c in cases:
@@ -53,7 +53,7 @@ def run(cases, tmp_dir, waves=3, timeout=900):
     src, dst = os.path.join(str(tmp_dir), "distance_cases.bin"), os.path.join(str(tmp_dir), "distance_results.bin")
     with open(src, "wb") as f:
         f.write(b"".join(blob))
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "distance_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = open(dst, "rb").read()
     out, at = [], 0

@@ -1,12 +1,14 @@
 // CPU fiber emulator for the wave-level kernels (TEST INFRASTRUCTURE ONLY, never linked into the product).
-// Compiles circkit_amd/csrc/canon_*.h against tests/emu/wave_prims_emu.h: each wavefront is 64 ucontext fibers scheduled
-// round-robin; every collective primitive is a rendezvous of all 64 fibers (a lane that skips a
-// collective deadlocks the wave, which is reported -- the same discipline the GPU build relies on).
+// Compiles circkit_amd/csrc/canon_*.h against tests/emu/wave_prims_emu.h: each wavefront is 64 ucontext fibers that switch at
+// collectives only, in the order of a named schedule (below; by default round-robin upward); every collective primitive is a
+// rendezvous of all 64 fibers (a lane that skips a collective deadlocks the wave, which is reported -- the same discipline the
+// GPU build relies on).
 #define CK_WAVE_PRIMS_OVERRIDE "../../tests/emu/wave_prims_emu.h"      // (relative to circkit_amd/csrc/wave_prims.h)
 #include <ucontext.h>
 #include <dlfcn.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 #include "../../circkit_amd/csrc/wave_prims.h"
 
@@ -14,6 +16,19 @@ namespace ck { namespace emu {
 // A workgroup = NW waves of 64 fibers.  Wave-level collectives rendezvous the 64 fibers of one wave; block_barrier()
 // rendezvous all fibers of the workgroup.  run_wave() is the 1-wave special case.
 constexpr int MAXW = 16;
+// The schedule: in which order the fibers of a workgroup get the processor between two collectives.  Chosen by name at the start
+// of every run_block -- emu_set_schedule()'s name if one is set, else the environment's CK_EMU_SCHEDULE, else "ascending":
+//   ascending     fiber 0 first, a yield or a finished fiber hands over to the next fiber upward (lane 0 .. 63, wave 0 first)
+//   descending    the last fiber first, hand over downward
+//   lone-wave     one wave keeps the processor: the next fiber is another lane of the current wave (downward) as long as one of
+//                 them can move; only when all its lanes wait in a block_barrier or have finished does another wave run, the
+//                 highest that can move, from its highest lane
+//   random:<seed> passes over the unfinished fibers, each pass in a fresh permutation drawn from splitmix64(seed): every
+//                 unfinished fiber gets its turn within one pass; the generator restarts with every run_block
+// A fiber that waits in a collective which is not complete yet is skipped, not resumed to find that out: what runs between the
+// collectives, and in which order, is for `ascending` exactly what resuming every waiting fiber in turn gives.
+enum Schedule { ASCENDING, DESCENDING, LONE_WAVE, RANDOM };
+enum Wait : uint8_t { RUNNING = 0, IN_COLLECTIVE, IN_BARRIER };
 struct WaveSync {
     uint64_t buf[2][64];
     int cnt[2];
@@ -28,26 +43,82 @@ struct BlockState {
     bool done[64 * MAXW];
     int bar_cnt[2];
     uint32_t bar_complete[2], bar_gen[64 * MAXW];
+    Wait wait[64 * MAXW];               // what the fiber waits in; its generation there is gen[f] - 1 / bar_gen[f] - 1
+    Schedule schedule = ASCENDING;
+    uint64_t rng = 0;
+    int pass[64 * MAXW], pass_n = 0, pass_at = 0;       // random: the current pass and how far it has come
     void (*body)(void*) = nullptr;
     void* arg = nullptr;
 };
 static BlockState* B = nullptr;
+static char schedule_name[64] = "";
 
 uint32_t cur_lane() { return (uint32_t)(B->cur & 63); }
 uint32_t cur_wave() { return (uint32_t)(B->cur >> 6); }
 
-static void yield_next(const char* what)
+static bool can_move(int f)
 {
-    int from = B->cur, nx = from;
-    for (int t = 0; t < B->nfib; ++t) {
-        nx = (nx + 1) % B->nfib;
-        if (!B->done[nx]) break;
+    if (B->done[f]) return false;
+    if (B->wait[f] == IN_COLLECTIVE) { const uint32_t g = B->gen[f] - 1; return B->ws[f >> 6].complete[g & 1] == g; }
+    if (B->wait[f] == IN_BARRIER) { const uint32_t g = B->bar_gen[f] - 1; return B->bar_complete[g & 1] == g; }
+    return true;
+}
+
+static uint64_t splitmix64()
+{
+    uint64_t z = (B->rng += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+static void new_pass()
+{
+    B->pass_n = B->pass_at = 0;
+    for (int f = 0; f < B->nfib; ++f)
+        if (!B->done[f]) B->pass[B->pass_n++] = f;
+    for (int i = B->pass_n - 1; i > 0; --i) {
+        const int j = (int)(splitmix64() % (uint64_t)(i + 1)), t = B->pass[i];
+        B->pass[i] = B->pass[j]; B->pass[j] = t;
     }
-    if (nx == from || B->done[nx]) {
-        fprintf(stderr, "emu: deadlock -- fiber %d (wave %d lane %d) waits in a %s the others never reach\n", from, from >> 6,
-                from & 63, what);
-        abort();
+}
+
+// the fiber that runs after `from` (which waits or has finished), or -1: a pass over all unfinished fibers found none that can move
+static int next_fiber(int from)
+{
+    const int n = B->nfib;
+    switch (B->schedule) {
+    case ASCENDING:
+        for (int t = 1; t < n; ++t) { const int f = (from + t) % n; if (can_move(f)) return f; }
+        return -1;
+    case DESCENDING:
+        for (int t = 1; t < n; ++t) { const int f = (from + n - t) % n; if (can_move(f)) return f; }
+        return -1;
+    case LONE_WAVE:
+        for (int t = 1; t < 64; ++t) { const int f = (from & ~63) | ((from - t) & 63); if (can_move(f)) return f; }
+        for (int f = n - 1; f >= 0; --f) if (can_move(f)) return f;
+        return -1;
+    case RANDOM:
+        for (int fresh = 0; fresh < 2; ++fresh) {       // the rest of this pass, then one whole new pass
+            while (B->pass_at < B->pass_n) { const int f = B->pass[B->pass_at++]; if (can_move(f)) return f; }
+            new_pass();
+        }
+        return -1;
     }
+    return -1;
+}
+
+static void deadlock(int f)
+{
+    fprintf(stderr, "emu: deadlock -- fiber %d (wave %d lane %d) waits in a %s the others never reach\n", f, f >> 6, f & 63,
+            B->wait[f] == IN_BARRIER ? "workgroup barrier" : "wave collective");
+    abort();
+}
+
+static void yield_next()
+{
+    const int from = B->cur, nx = next_fiber(from);
+    if (nx < 0) deadlock(from);
     B->cur = nx;
     swapcontext(&B->ctx[from], &B->ctx[nx]);
 }
@@ -62,7 +133,6 @@ void gather(uint64_t v, uint64_t out[64])
     // every lane must be in the SAME collective: compare the call sites (build with -O0 -DCK_EMU_CHECK_SITES)
     static void* site[MAXW][2][64];
     site[f >> 6][s][l] = __builtin_return_address(1);
-    if (w.cnt[s] > 0 && site[f >> 6][s][l] != site[f >> 6][s][(l + 63) & 63] && false) {}
 #endif
     w.buf[s][l] = v;
     if (++w.cnt[s] == 64) {
@@ -78,7 +148,9 @@ void gather(uint64_t v, uint64_t out[64])
 #endif
         w.complete[s] = g; w.cnt[s] = 0;
     }
-    while (w.complete[s] != g) yield_next("wave collective");
+    B->wait[f] = IN_COLLECTIVE;
+    while (w.complete[s] != g) yield_next();
+    B->wait[f] = RUNNING;
     for (int i = 0; i < 64; ++i) out[i] = w.buf[s][i];
 }
 
@@ -88,7 +160,9 @@ void block_barrier()
     const uint32_t g = B->bar_gen[f]++;
     const int s = g & 1;
     if (++B->bar_cnt[s] == B->nfib) { B->bar_complete[s] = g; B->bar_cnt[s] = 0; }
-    while (B->bar_complete[s] != g) yield_next("workgroup barrier");
+    B->wait[f] = IN_BARRIER;
+    while (B->bar_complete[s] != g) yield_next();
+    B->wait[f] = RUNNING;
 }
 
 static void trampoline()
@@ -96,11 +170,25 @@ static void trampoline()
     const int f = B->cur;
     B->body(B->arg);
     B->done[f] = true;
-    for (int t = 1; t <= B->nfib; ++t) {        // hand over to the next unfinished fiber, or back to main
-        int nx = (f + t) % B->nfib;
-        if (!B->done[nx]) { B->cur = nx; setcontext(&B->ctx[nx]); }
-    }
+    const int nx = next_fiber(f);               // hand over to the next fiber that can move, or back to main
+    if (nx >= 0) { B->cur = nx; setcontext(&B->ctx[nx]); }
+    for (int i = 0; i < B->nfib; ++i)
+        if (!B->done[i]) deadlock(i);           // the unfinished ones all wait, and nothing is left that would release them
     setcontext(&B->main_ctx);
+}
+
+static void read_schedule()
+{
+    const char* name = schedule_name[0] ? schedule_name : getenv("CK_EMU_SCHEDULE");
+    if (!name || !name[0] || !strcmp(name, "ascending")) B->schedule = ASCENDING;
+    else if (!strcmp(name, "descending")) B->schedule = DESCENDING;
+    else if (!strcmp(name, "lone-wave")) B->schedule = LONE_WAVE;
+    else if (!strncmp(name, "random:", 7) && name[7]) {
+        char* end;
+        B->rng = strtoull(name + 7, &end, 10);
+        if (*end) { fprintf(stderr, "emu: bad seed in schedule \"%s\"\n", name); abort(); }
+        B->schedule = RANDOM;
+    } else { fprintf(stderr, "emu: unknown schedule \"%s\" (ascending, descending, lone-wave, random:<seed>)\n", name); abort(); }
 }
 
 void run_block(void (*body)(void*), void* arg, int nwaves)
@@ -117,21 +205,29 @@ void run_block(void (*body)(void*), void* arg, int nwaves)
     st.bar_cnt[0] = st.bar_cnt[1] = 0;
     st.bar_complete[0] = 0xFFFFFFFFu; st.bar_complete[1] = 0xFFFFFFFEu;
     for (int i = 0; i < st.nfib; ++i) {
-        st.gen[i] = 0; st.bar_gen[i] = 0; st.done[i] = false;
+        st.gen[i] = 0; st.bar_gen[i] = 0; st.done[i] = false; st.wait[i] = RUNNING;
         getcontext(&st.ctx[i]);
         st.ctx[i].uc_stack.ss_sp = st.stacks.data() + i * STK;
         st.ctx[i].uc_stack.ss_size = STK;
         st.ctx[i].uc_link = &st.main_ctx;
         makecontext(&st.ctx[i], (void (*)())trampoline, 0);
     }
-    st.cur = 0;
-    swapcontext(&st.main_ctx, &st.ctx[0]);
+    read_schedule();
+    st.cur = st.schedule == ASCENDING ? 0 : st.nfib - 1;
+    if (st.schedule == RANDOM) { new_pass(); st.cur = st.pass[st.pass_at++]; }
+    swapcontext(&st.main_ctx, &st.ctx[st.cur]);
     for (int i = 0; i < st.nfib; ++i)
         if (!st.done[i]) { fprintf(stderr, "emu: fiber %d did not finish\n", i); abort(); }
 }
 
 void run_wave(void (*body)(void*), void* arg) { run_block(body, arg, 1); }
 }}  // namespace ck::emu
+
+// The schedule of every later run_block in this process (tests/emu/emu.py's scheduled()); NULL or "" = back to the environment's.
+extern "C" void emu_set_schedule(const char* name)
+{
+    snprintf(ck::emu::schedule_name, sizeof ck::emu::schedule_name, "%s", name ? name : "");
+}
 
 #include "../../circkit_amd/csrc/canon_core.h"
 #include "../../circkit_amd/csrc/canon_fast.h"

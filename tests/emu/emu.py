@@ -1,4 +1,5 @@
 """Loads the CPU fiber emulator of the wave kernels (tests only)."""
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -21,6 +22,34 @@ def build():
         # source abort the test process (sanitizers on the CPU build only -- the GPU pool offers none)
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared"] + SANITIZE + ["-o", _SO, os.path.join(_HERE, "emu.cpp")])
     return _SO
+
+
+# The fiber schedules of emu.cpp's run_block: SCHEDULES is the matrix the units run under besides the default "ascending".
+SCHEDULES = ("descending", "lone-wave", "random:1", "random:2")
+
+
+def child_env(schedule):
+    """The environment of a stand-alone emulator program that runs under `schedule` (None: this process's own, unchanged)."""
+    if schedule is None:
+        return None
+    env = dict(os.environ)
+    env["CK_EMU_SCHEDULE"] = schedule
+    return env
+
+
+@contextlib.contextmanager
+def scheduled(schedule):
+    """Every run_block of the in-process emulator libraries runs under `schedule` inside the block (None: no change)."""
+    if schedule is None:
+        yield
+        return
+    lib = ctypes.CDLL(build(), mode=ctypes.RTLD_GLOBAL)
+    lib.emu_set_schedule.argtypes = [ctypes.c_char_p]
+    lib.emu_set_schedule(schedule.encode())
+    try:
+        yield
+    finally:
+        lib.emu_set_schedule(None)
 
 
 _lib = None
@@ -54,7 +83,7 @@ def alpha_rule(data, offsets):
 
 def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False, flags=0, staged=1, want_aux=True,
                        base_shift=0, lead=0, alpha=None, solo=True, mixed=False, hash_only=False, want_index=None, want_strand=None,
-                       want_bytes=True):
+                       want_bytes=True, schedule=None):
     global _lib
     if _lib is None:
         _lib = ctypes.CDLL(build())
@@ -90,10 +119,11 @@ def canonicalize_batch(data, offsets, slice_dw=1024, n_waves=3, want_hash=False,
     # want_aux=False: no rotation index / strand outputs -- the streaming kernel's leaner builds (see launch_canon)
     # hash_only: no canonical bytes anywhere (launch_canon with d_hash and without d_out): views + the xxh3 pass over them
     inp = pad.copy()
-    st = _lib.emu_canonicalize_batch(pad.ctypes.data, offsets.ctypes.data, n, out.ctypes.data if want_bytes else None,
-                                     idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None,
-                                     hs.ctypes.data if want_hash else None,
-                                     slice_dw, n_waves, ctypes.byref(ndef), flags, ctypes.byref(nfast), ctypes.byref(nfused), int(staged), ctypes.byref(nresc), int(bool(alpha)) | (0 if solo else 2) | (4 if mixed else 0))
+    with scheduled(schedule):
+        st = _lib.emu_canonicalize_batch(pad.ctypes.data, offsets.ctypes.data, n, out.ctypes.data if want_bytes else None,
+                                         idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None,
+                                         hs.ctypes.data if want_hash else None,
+                                         slice_dw, n_waves, ctypes.byref(ndef), flags, ctypes.byref(nfast), ctypes.byref(nfused), int(staged), ctypes.byref(nresc), int(bool(alpha)) | (0 if solo else 2) | (4 if mixed else 0))
     assert st >= 0, "emulator rejected the launch (unknown `staged` geometry?)"
     global last_fast_count, last_fused_hash_count, last_rescued_count
     last_rescued_count = nresc.value
@@ -122,7 +152,7 @@ S_OUT, S_IDX, S_STRAND = 0x3F, 0xFFFFFFFF, 0xFF
 
 
 def tier_footprint(data, offsets, slice_dw, kind="tier", entries=None, solo=True, team4=True, flags=0, want_bytes=True, want_index=True,
-                   want_strand=True, base_shift=0):
+                   want_strand=True, base_shift=0, schedule=None):
     """One 4-wave workgroup with its LDS pre-filled with FOOTPRINT_PATTERN and a guard region behind the four slices
     (emu_tier_footprint).  kind "tier": canon_kernel<4>'s loop and team pass over the list `entries` (record indices, flag bits
     allowed; entry i is wave i % 4's); "mixed" / "mixed_n": the mixed-length kernel's pure / N build over all records (record i is
@@ -152,10 +182,11 @@ def tier_footprint(data, offsets, slice_dw, kind="tier", entries=None, solo=True
     guard = ctypes.c_uint32(0)
     deferred = np.zeros(max(len(ent), n) + 4, dtype=np.uint32)
     ndef = ctypes.c_uint32(0)
-    st = fn(pad.ctypes.data, offsets.ctypes.data, n, ent.ctypes.data if len(ent) else None, len(ent), out.ctypes.data if want_bytes else None,
-            idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None, None, int(slice_dw),
-            {"tier": 0, "mixed": 1, "mixed_n": 2}[kind], int(bool(solo)) | (2 if team4 else 0), int(flags), FOOTPRINT_PATTERN, hw.ctypes.data,
-            ctypes.byref(guard), deferred.ctypes.data, ctypes.byref(ndef))
+    with scheduled(schedule):
+        st = fn(pad.ctypes.data, offsets.ctypes.data, n, ent.ctypes.data if len(ent) else None, len(ent), out.ctypes.data if want_bytes else None,
+                idx.ctypes.data if want_index else None, strand.ctypes.data if want_strand else None, None, int(slice_dw),
+                {"tier": 0, "mixed": 1, "mixed_n": 2}[kind], int(bool(solo)) | (2 if team4 else 0), int(flags), FOOTPRINT_PATTERN, hw.ctypes.data,
+                ctypes.byref(guard), deferred.ctypes.data, ctypes.byref(ndef))
     assert st >= 0
     assert (out[len(data):] == S_OUT).all() and (raw_out[:skew] == S_OUT).all(), "kernel wrote outside the batch"
     assert (idx[n:] == S_IDX).all() and (strand[n:] == S_STRAND).all(), "kernel wrote a per-record output past record n - 1"

@@ -42,7 +42,7 @@ def constants():
     return {"TILE_BYTES": int(out[0]), "SCAN_WG": int(out[1]), "WAVES": int(out[2])}
 
 
-def run(cases, tmp_dir, timeout=900):
+def run(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(text, first_chunk, final_chunk, dict(in_shift=, out_shift=, record_capacity=, byte_capacity=))].  Returns per case
     dict(refused, records, bytes, consumed, offsets, data, head, raw); asserts the program's own checks."""
     src, dst = os.path.join(str(tmp_dir), "fasta_cases.bin"), os.path.join(str(tmp_dir), "fasta_results.bin")
@@ -52,7 +52,7 @@ def run(cases, tmp_dir, timeout=900):
             head = [len(text), int(bool(first)) | 2 * int(bool(final)), place.get("in_shift", 0), place.get("out_shift", 0),
                     place.get("record_capacity", EXACT), place.get("byte_capacity", EXACT)]
             f.write(np.array(head, dtype=np.uint64).tobytes() + bytes(text))
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "fasta_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = open(dst, "rb").read()
     out, at = [], 0

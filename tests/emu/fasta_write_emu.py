@@ -43,7 +43,7 @@ def constants():
     return dict(zip(("TILE_BYTES", "WRITE_WAVES", "SCAN_TILE", "SCAN_WG"), (int(v) for v in out)))
 
 
-def run(cases, tmp_dir, timeout=900):
+def run(cases, tmp_dir, timeout=900, schedule=None):
     """cases: tests/fasta_write_sets.py Case objects.  Returns per case (text | None when refused, out_offsets, total, n_invalid,
     refused); asserts the program's own checks."""
     src, dst = os.path.join(str(tmp_dir), "fasta_write_cases.bin"), os.path.join(str(tmp_dir), "fasta_write_results.bin")
@@ -63,7 +63,7 @@ def run(cases, tmp_dir, timeout=900):
                 f.write(c.labels.tobytes())
             if c.body is not None:
                 f.write(c.offsets.tobytes() + c.body.tobytes())
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "fasta_write_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = open(dst, "rb").read()
     out, at = [], 0

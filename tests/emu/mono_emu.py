@@ -29,7 +29,7 @@ def build():
 _lib = None
 
 
-def monomerize_batch(data, offsets, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False, base_shift=0, lead=0):
+def monomerize_batch(data, offsets, seed_len=10, max_mismatch=None, min_identity=None, sensitive=False, base_shift=0, lead=0, schedule=None):
     """The wave routine on every record of a CSR batch: a uint32 array (NONE = None).  base_shift: misalignment of the
     payload pointer; lead: canary bytes in front of the first record.  The input is surrounded by canaries and checked to
     be unchanged; the output array has canaries round it."""
@@ -51,9 +51,10 @@ def monomerize_batch(data, offsets, seed_len=10, max_mismatch=None, min_identity
     pad[lead:lead + len(data)] = data
     before = raw.copy()
     out = np.full(64 + n + 64, 0xA5A5A5A5, dtype=np.uint32)
-    rc = _lib.emu_monomerize_batch(pad.ctypes.data, offsets.ctypes.data, n, int(seed_len), int(min_identity is not None),
-                                   int(max_mismatch or 0), float(min_identity) if min_identity is not None else 0.0,
-                                   int(bool(sensitive)), out[64:].ctypes.data)
+    with emu.scheduled(schedule):
+        rc = _lib.emu_monomerize_batch(pad.ctypes.data, offsets.ctypes.data, n, int(seed_len), int(min_identity is not None),
+                                       int(max_mismatch or 0), float(min_identity) if min_identity is not None else 0.0,
+                                       int(bool(sensitive)), out[64:].ctypes.data)
     assert rc == 0, "the lanes of a wave disagree on the result" if rc == -1 else "emulator refused the batch"
     assert np.array_equal(raw, before), "the routine wrote into its input"
     assert (out[:64] == 0xA5A5A5A5).all() and (out[64 + n:] == 0xA5A5A5A5).all(), "wrote outside the output array"

@@ -40,11 +40,11 @@ def constants():
     return tuple(int(v) for v in out)
 
 
-def _run(blob, tmp_dir, timeout):
+def _run(blob, tmp_dir, timeout, schedule=None):
     src, dst = os.path.join(str(tmp_dir), "prealign_cases.bin"), os.path.join(str(tmp_dir), "prealign_results.bin")
     with open(src, "wb") as f:
         f.write(blob)
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "prealign_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     return open(dst, "rb").read()
 
@@ -53,7 +53,7 @@ def _u64(values):
     return np.array([int(v) for v in values], dtype=np.uint64).tobytes()
 
 
-def run_anchors(cases, tmp_dir, timeout=900):
+def run_anchors(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(records, k, log2_bins, seed, lead, short_grid, long_grid, want_counts)].  Returns per case (rows, anchors, counts or
     None, (valid, unprocessed, long))."""
     blob = [_u64([len(cases)])]
@@ -61,7 +61,7 @@ def run_anchors(cases, tmp_dir, timeout=900):
         offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
         offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
         blob += [_u64([0, len(seqs), int(offsets[-1]), lead, k, lb, seed, sg, lg, int(bool(wc))]), offsets.tobytes(), b"".join(seqs)]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for c, (seqs, k, lb, seed, lead, sg, lg, wc) in enumerate(cases):
         rc, valid, unprocessed, n_long = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=4, offset=at))
@@ -81,7 +81,7 @@ def run_anchors(cases, tmp_dir, timeout=900):
     return out
 
 
-def run_votes(cases, tmp_dir, timeout=900):
+def run_votes(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(rows, anchors, offsets, k, min_votes, pairs, waves)].  Returns per case (windows, scores, aligned, invalid)."""
     blob = [_u64([len(cases)])]
     shaped = []
@@ -94,7 +94,7 @@ def run_votes(cases, tmp_dir, timeout=900):
         shaped.append(len(pairs))
         blob += [_u64([1, len(rows), rows.shape[1].bit_length() - 1, k, mv, len(pairs), waves]), rows.tobytes(), anchors.tobytes(), offsets.tobytes(),
                  pairs.tobytes()]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for c, m in enumerate(shaped):
         rc, aligned, invalid = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=3, offset=at))
@@ -109,13 +109,13 @@ def run_votes(cases, tmp_dir, timeout=900):
     return out
 
 
-def run_labels(cases, tmp_dir, timeout=300):
+def run_labels(cases, tmp_dir, timeout=300, schedule=None):
     """cases: [(labels, waves)].  Returns per case the pairs (n, 2)."""
     blob = [_u64([len(cases)])]
     for labels, waves in cases:
         labels = np.ascontiguousarray(labels, dtype=np.uint64)
         blob += [_u64([2, len(labels), waves]), labels.tobytes()]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for c, (labels, _) in enumerate(cases):
         rc = int(np.frombuffer(raw, dtype=np.uint64, count=1, offset=at)[0])

@@ -30,7 +30,7 @@ def build():
     return _BIN
 
 
-def run(hdr, inputs, mems, nwaves, out_w, mem_bytes, tmp_dir, timeout=600):
+def run(hdr, inputs, mems, nwaves, out_w, mem_bytes, tmp_dir, timeout=600, schedule=None):
     """The arguments and results of tests/prims_probe.py's run(), with `nwaves` in place of the threads: hdr (n, 4) uint32 (op,
     mode, mem slot, 0: slot 0 = no memory), inputs (n, 64, IN_W) uint32, mems (slots, mem_bytes) uint8.  Returns out (n, nwaves,
     64, out_w) uint32 and the memory afterwards (slots, nwaves, mem_bytes) uint8; asserts the program's own checks."""
@@ -45,7 +45,7 @@ def run(hdr, inputs, mems, nwaves, out_w, mem_bytes, tmp_dir, timeout=600):
             f.write(i.tobytes())
             if h[2]:
                 f.write(mems[h[2]].tobytes())
-    r = subprocess.run([build(), str(nwaves), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), str(nwaves), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "prims_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = np.fromfile(dst, dtype=np.uint8)
     out = np.zeros((len(hdr), nwaves, 64, out_w), dtype=np.uint32)

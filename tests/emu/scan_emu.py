@@ -78,7 +78,7 @@ def run_both(cases, tmp_dir):
     return up
 
 
-def run(cases, tmp_dir, descending=False, timeout=600):
+def run(cases, tmp_dir, descending=False, timeout=600, schedule=None):
     """cases: [(routine, configuration, data, extra)]: data = the WG elements / the n sums / the n item words / the n lengths,
     extra = tile_base's sums (None otherwise).  descending: fiber f is thread WG - 1 - f (scan_emu_main.cpp).  Returns per case
       block_scan, sums_exclusive   (elements, totals: one per thread)
@@ -94,7 +94,7 @@ def run(cases, tmp_dir, descending=False, timeout=600):
             tail = op.flat(extra) if extra is not None else []
             f.write(np.array([routine, config, len(data), len(extra) if extra is not None else 0], dtype=np.uint64).tobytes())
             f.write(np.array(words + tail, dtype=np.uint64).tobytes())
-    r = subprocess.run([build()] + (["--descending"] if descending else []) + [src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build()] + (["--descending"] if descending else []) + [src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "scan_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = np.fromfile(dst, dtype=np.uint64)
     out, at = [], 0

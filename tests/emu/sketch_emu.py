@@ -39,11 +39,11 @@ def constants():
     return int(out[0]), int(out[1])
 
 
-def _run(blob, tmp_dir, timeout):
+def _run(blob, tmp_dir, timeout, schedule=None):
     src, dst = os.path.join(str(tmp_dir), "sketch_cases.bin"), os.path.join(str(tmp_dir), "sketch_results.bin")
     with open(src, "wb") as f:
         f.write(blob)
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "sketch_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     return open(dst, "rb").read()
 
@@ -52,7 +52,7 @@ def _u64(values):
     return np.array([int(v) for v in values], dtype=np.uint64).tobytes()
 
 
-def run_sketch(cases, tmp_dir, timeout=900):
+def run_sketch(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(data, offsets, dict(k=, log2_bins=, seed=), dict(lead=, in_shift=, short_grid=, long_grid=, counts=))].  The
     offsets may name more bytes than `data` holds (a crafted record that must not be read).  Returns per case (rows (n, bins),
     counts | None, valid, unprocessed, n_long); asserts the program's own checks."""
@@ -62,7 +62,7 @@ def run_sketch(cases, tmp_dir, timeout=900):
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         blob += [_u64([0, len(offsets) - 1, len(data), place.get("lead", 0), place.get("in_shift", 0), p["k"], p["log2_bins"], p.get("seed", 0),
                        place.get("short_grid", 3), place.get("long_grid", 5), int(place.get("counts", True))]), offsets.tobytes(), data.tobytes()]
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for k, (_, offsets, p, place) in enumerate(cases):
         rc, valid, unprocessed, n_long = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=4, offset=at))
@@ -80,7 +80,7 @@ def run_sketch(cases, tmp_dir, timeout=900):
     return out
 
 
-def run_compare(cases, tmp_dir, timeout=900):
+def run_compare(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(rows_a, rows_b | None for the same array, pairs (m, 2), waves)].  Returns per case (match, filled, n_invalid)."""
     blob = [_u64([len(cases)])]
     for a, b, pairs, waves in cases:
@@ -93,7 +93,7 @@ def run_compare(cases, tmp_dir, timeout=900):
             assert b.shape[1] == bins
             blob.append(b.tobytes())
         blob.append(pairs.tobytes())
-    raw = _run(b"".join(blob), tmp_dir, timeout)
+    raw = _run(b"".join(blob), tmp_dir, timeout, schedule)
     out, at = [], 0
     for k, (_, _, pairs, _) in enumerate(cases):
         rc, bad = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=2, offset=at))

@@ -48,7 +48,7 @@ def params_bytes(aa, unknown, first_as_m):
     return aa + unknown + bytes([int(bool(first_as_m))]) + bytes(6)
 
 
-def run(cases, tmp_dir, timeout=900):
+def run(cases, tmp_dir, timeout=900, schedule=None):
     """cases: [(data, offsets, windows, dict(lead=, in_shift=, out_shift=, capacity=), (aa, unknown, first_as_m))].  Returns per case
     (residues | None when refused, out_offsets, total, n_invalid); asserts the program's own checks."""
     src, dst = os.path.join(str(tmp_dir), "translate_cases.bin"), os.path.join(str(tmp_dir), "translate_results.bin")
@@ -62,7 +62,7 @@ def run(cases, tmp_dir, timeout=900):
             head = [len(offsets) - 1, len(windows), len(data), place.get("lead", 0), place.get("in_shift", 0), place.get("out_shift", 0),
                     place.get("capacity", EXACT)]
             f.write(np.array(head, dtype=np.uint64).tobytes() + params_bytes(*code) + offsets.tobytes() + data.tobytes() + windows.tobytes())
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "translate_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = open(dst, "rb").read()
     out, at = [], 0

@@ -37,15 +37,17 @@ def lib():
     return _lib
 
 
-def decide(lengths, first_seen, base_index=0):
-    """(kept bool[n], written length uint64[n]) as ck_compact::decide_uniq answers record by record."""
+def decide(lengths, first_seen, base_index=0, schedule=None):
+    """(kept bool[n], written length uint64[n]) as ck_compact::decide_uniq answers record by record.  The decision is per record
+    and runs no fibers today; `schedule` is set round the call all the same, so that it holds the day the routine gains a collective."""
     L = lib()
     lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
     first_seen = np.ascontiguousarray(first_seen, dtype=np.uint64)
     n = len(lengths)
     assert len(first_seen) == n
     w = np.full(n + 2, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
-    L.emu_uniq_decide(lengths.ctypes.data, first_seen.ctypes.data, int(base_index), n, w[1:].ctypes.data)
+    with emu.scheduled(schedule):
+        L.emu_uniq_decide(lengths.ctypes.data, first_seen.ctypes.data, int(base_index), n, w[1:].ctypes.data)
     assert w[0] == 0x5A5A5A5A5A5A5A5A and w[n + 1] == 0x5A5A5A5A5A5A5A5A
     bit = np.uint64(L.emu_uniq_written_bit())
     return (w[1:n + 1] & bit) != 0, w[1:n + 1] & ~bit

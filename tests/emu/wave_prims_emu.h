@@ -1,5 +1,5 @@
 // wave_prims_emu.h -- CPU fiber implementation of the interface of circkit_amd/csrc/wave_prims.h (TEST INFRASTRUCTURE
-// ONLY): every wavefront is 64 ucontext fibers scheduled round-robin, every collective a rendezvous of the 64 fibers
+// ONLY): every wavefront is 64 ucontext fibers scheduled by tests/emu/emu.cpp, every collective a rendezvous of the 64 fibers
 // (a lane that skips one deadlocks the wave, which is reported).  Included through CK_WAVE_PRIMS_OVERRIDE by
 // tests/emu/emu.cpp; never part of the product build.
 #pragma once

@@ -53,7 +53,7 @@ def of_records(lengths, kind, bases=0, percent=0.0):
     return w
 
 
-def run(cases, tmp_dir, timeout=600):
+def run(cases, tmp_dir, timeout=600, schedule=None):
     """cases: [(data, offsets, windows, dict(lead=, in_shift=, out_shift=, capacity=))].  Returns per case (out_bytes | None when
     refused, out_offsets, total, n_invalid); asserts the program's own checks."""
     src, dst = os.path.join(str(tmp_dir), "windows_cases.bin"), os.path.join(str(tmp_dir), "windows_results.bin")
@@ -67,7 +67,7 @@ def run(cases, tmp_dir, timeout=600):
             head = [len(offsets) - 1, len(windows), len(data), place.get("lead", 0), place.get("in_shift", 0), place.get("out_shift", 0),
                     place.get("capacity", EXACT)]
             f.write(np.array(head, dtype=np.uint64).tobytes() + offsets.tobytes() + data.tobytes() + windows.tobytes())
-    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([build(), src, dst], capture_output=True, text=True, timeout=timeout, env=emu.child_env(schedule))
     assert r.returncode == 0, "windows_emu_main failed (%d): %s" % (r.returncode, r.stderr[-2000:])
     raw = open(dst, "rb").read()
     out, at = [], 0
