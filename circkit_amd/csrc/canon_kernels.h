@@ -11,6 +11,7 @@
 #include "canon_mixed.h"
 #include "xxh3_core.h"
 #include "canon_config.h"
+#include "canon_plan.h"
 
 namespace {
 
@@ -215,16 +216,17 @@ __global__ __launch_bounds__(64) void xxh3_list_kernel(const uint8_t* bytes, con
         if (ck::lane_id() == 0) out[r] = h;
     }
 }
-// ctl: [0] two-word records among the samples, [1] longer ones, [2] arrival ticket, [3] content samples with a byte
-// outside ACGT -- all zero on entry and on exit; *mode receives stream_mode() | alpha_mode() of the samples (written by
-// the workgroup that arrives last), counters[0] (records beyond the LDS tiers) and counters[3] (records nothing could
-// take) are zeroed: nothing of this batch has touched them yet, nothing of the previous one is still running.
+// ctl: the ctx's count block (canon_plan.h CountWord: two-word records among the samples, longer ones, arrival ticket, content
+// samples with a byte outside ACGT, short records) -- all zero on entry and on exit; *mode receives batch_mode_of() of the
+// samples (written by the workgroup that arrives last); the counters a batch starts from zero (CTR_PASSED_ON, CTR_TIERS_BUSY,
+// CTR_UNPROCESSED, the mixed ticket) are zeroed: nothing of this batch has touched them yet, nothing of the previous one is
+// still running.
 __global__ __launch_bounds__(1024) void stream_count_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n, uint32_t* ctl,
                                                             uint32_t* mode, uint32_t* counters, uint32_t hashed)
 {
     __shared__ uint32_t blk[4];
     if (threadIdx.x < 4) blk[threadIdx.x] = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 3) { counters[0] = 0; counters[1] = 0; counters[3] = 0; counters[16] = 0; counters[17] = 0; }      // ([16], [17]: the mixed N builds' segment ticket -- self-zeroing, zeroed here as well)
+    if (blockIdx.x == 0 && threadIdx.x == 3) { counters[CTR_PASSED_ON] = 0; counters[CTR_TIERS_BUSY] = 0; counters[CTR_UNPROCESSED] = 0; counters[CTR_MIXED_TICKET] = 0; counters[CTR_MIXED_TICKET + 1] = 0; }      // (the mixed N builds' segment ticket is self-zeroing, zeroed here as well)
     __syncthreads();
     const uint32_t shift = count_shift(n);
     const uint64_t ns = count_samples(n);
@@ -260,17 +262,17 @@ __global__ __launch_bounds__(1024) void stream_count_kernel(const uint8_t* __res
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (blk[0]) atomicAdd(ctl, blk[0]);
-        if (blk[1]) atomicAdd(ctl + 1, blk[1]);
-        if (blk[2]) atomicAdd(ctl + 3, blk[2]);
-        if (blk[3]) atomicAdd(ctl + 5, blk[3]);
+        if (blk[0]) atomicAdd(ctl + CNT_TWO_WORD, blk[0]);
+        if (blk[1]) atomicAdd(ctl + CNT_LONGER, blk[1]);
+        if (blk[2]) atomicAdd(ctl + CNT_NOT_ACGT, blk[2]);
+        if (blk[3]) atomicAdd(ctl + CNT_SHORT, blk[3]);
         // arrival ticket: the adds above are device-scope atomics (performed at the memory side, in order behind this
         // wave's earlier ones once drained), the last arriver reads the sums with atomics as well
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (atomicAdd(ctl + 2, 1u) == gridDim.x - 1) {
-            const uint32_t t2 = atomicExch(ctl, 0u), tl = atomicExch(ctl + 1, 0u), tb = atomicExch(ctl + 3, 0u), ts = atomicExch(ctl + 5, 0u);
+        if (atomicAdd(ctl + CNT_TICKET, 1u) == gridDim.x - 1) {
+            const uint32_t t2 = atomicExch(ctl + CNT_TWO_WORD, 0u), tl = atomicExch(ctl + CNT_LONGER, 0u), tb = atomicExch(ctl + CNT_NOT_ACGT, 0u), ts = atomicExch(ctl + CNT_SHORT, 0u);
             *mode = batch_mode_of(t2, tl, ns, tb, nc, ts, hashed != 0);
-            atomicExch(ctl + 2, 0u);
+            atomicExch(ctl + CNT_TICKET, 0u);
         }
     }
 }
@@ -290,10 +292,9 @@ __global__ __launch_bounds__(256) void canon_rescue_kernel(ck::CanonArgs a, cons
                                                            uint32_t* tiers_busy)
 {
     const uint32_t mode = batch_mode(mode_word, host_mode);
-    if (!AUX && ((mode & MODE_ALPHA) != 0) != ALPHA) return;            // the other build has this batch
-    if (!AUX && (mode & 3) == 3) return;                                 // ... or a canon_mixed kernel (either alphabet, with or without the XXH3)
+    if (!rescue_owns(AUX, ALPHA, mode)) return;                          // the other build has this batch, or a canon_mixed kernel
     if (blockIdx.x == 0 && threadIdx.x == 0) *mode_out = (host_mode >> 31) ? *mode_word : mode;     // for circkit_ctx_last_batch_mode() and the next batch's launch: the batch's OWN mode
-    const bool all_records = (mode & 3) == 3;                           // the streaming kernel stood this batch out
+    const bool all_records = AUX && (mode & 3) == 3;                    // the streaming kernel stood this batch out (only the AUX build owns such a batch)
     if (!all_records) {
         // the ordinary batch leaves this pass (next to) nothing: one parallel look at the workgroup's segments first
         const uint32_t mine = blockIdx.x < a.in_nseg ? (a.in_nseg - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
@@ -353,7 +354,7 @@ __device__ __forceinline__ void canon_mixed_body(const ck::CanonArgs& a, const u
 {
     constexpr int WPB = mixed_wpb(NM, HASH);
     const uint32_t mode = batch_mode(mode_word, host_mode);
-    if ((mode & 3) != 3 || ((mode & MODE_ALPHA) != 0) != NM) return;
+    if (!mixed_owns(NM, mode)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) *mode_out = (host_mode >> 31) ? *mode_word : mode;
 #ifdef CK_MIXED_TIMELINE
     const uint64_t tl_start = wall_clock64();
@@ -423,18 +424,13 @@ CK_MIXED_KERNEL(canon_mixed_nh_kernel, true, true, CK_MIXED_NM_VGPR)
 // ALPHA (ROWS = 1, no index / strand outputs): the build for batches with MODE_ALPHA -- records with N or '-' take the
 // 4-bit register routine inside the staged loop.  The builds without it answer for every other batch, MODE_ALPHA or not.
 template <class StreamC, bool HASH, bool AUX, bool PERSIST, bool ALPHA = false>
-__global__ __launch_bounds__(StreamC::WPB * 64, (HASH && !AUX && StreamC::ROWS == 1 && (ALPHA || StreamC::RPW == 2)) ? CK_PAIR_WPE : (StreamC::WPB >= 8 || (ALPHA && !HASH && !AUX)) ? CK_FAST_WPE : 4) void canon_stream_kernel(ck::CanonArgs a, const uint32_t* __restrict__ mode,
+__global__ __launch_bounds__(StreamC::WPB * 64, (StreamBuild<StreamC, HASH, AUX, ALPHA>::WPE)) void canon_stream_kernel(ck::CanonArgs a, const uint32_t* __restrict__ mode,
                                                                                                              uint32_t host_mode, uint32_t nvb)
 {
-    const uint32_t bm = batch_mode(mode, host_mode);
-    if ((bm & 3) != (uint32_t)StreamC::ROWS) return;                             // the other build (or none) has this batch
-    constexpr bool HAS_ALPHA_TWIN = StreamC::ROWS == 1 && !AUX;
-    if (HAS_ALPHA_TWIN && ((bm & MODE_ALPHA) != 0) != ALPHA) return;
-    if (HAS_ALPHA_TWIN && !ALPHA && !HASH && ((bm & MODE_SHORT) != 0) != (StreamC::RPW == 2)) return;       // bytes only: the pair build has the batches of short records
-    constexpr bool GH = CK_GROUP_HASH && HASH && !AUX && StreamC::ROWS == 1 && (StreamC::RPW == 1 || !ALPHA) && StreamC::GROUP <= 16;
-    constexpr bool PAIR = GH && StreamC::RPW == 2;                                // canon_pair.h: two records per wave
-    constexpr bool PAIR_B = !HASH && !AUX && !ALPHA && StreamC::ROWS == 1 && StreamC::RPW == 2;    // the bytes-only pair build: MODE_SHORT batches
-    __shared__ __attribute__((aligned(16))) uint32_t lds[StreamC::LDS_DW + (GH ? ck::gh_lds_dw<(int)StreamC::GROUP, PAIR>() : PAIR_B ? StreamC::GROUP * ck::PAIR_SCRATCH_DW : 0)];
+    using Build = StreamBuild<StreamC, HASH, AUX, ALPHA>;
+    if (!Build::owns(batch_mode(mode, host_mode))) return;                       // another build (or none) has this batch
+    constexpr bool GH = Build::GH, PAIR = Build::PAIR;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[Build::LDS_DW];
     uint32_t* lut = lds + StreamC::NBUF * StreamC::BUF_DW;
     uint32_t* blk_count = lut + ck::FAST_LUT_DW;
     uint32_t* gh = lds + StreamC::LDS_DW;

@@ -117,7 +117,7 @@ CK_DEV StreamGroup stream_issue(const CanonArgs& a, const StreamBase& sb, uint32
 // Test build (tests/poison.py, never the product library): a guard for the hand-counted vmcnt protocol below.  Right before
 // a ring image's DMA is re-issued every wave overwrites its slots of that image with a pattern no payload byte can form
 // (the writes are waited for, so the DMA data lands on top of them); a record whose aligned chunk still reads the pattern
-// when it is packed was consumed before its DMA had landed -- counted in status[9] (d_counters[12]), read back by
+// when it is packed was consumed before its DMA had landed -- counted in status[9] (canon_plan.h CTR_POISON), read back by
 // circkit_debug_poison_count.  On the CPU emulator the DMA is a synchronous memcpy, so only the GPU can tell.
 constexpr uint32_t CK_POISON = 0xFEFEFEFEu;
 template <class C>

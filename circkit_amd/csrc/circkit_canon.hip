@@ -1,4 +1,4 @@
-// circkit_canon.hip -- canonicalize: the host side of a batch (launch_canon, one function per stage), of a single record
+// circkit_canon.hip -- canonicalize: the host side of a batch (launch_canon, one function per stage, the front stages by canon_plan.h's plan), of a single record
 // (launch_single) and of a host-buffer batch in parts (host_batch), and the C ABI of include/circkit.h that runs or reports on
 // that work.  The kernels are canon_kernels.h, the constants and the batch geometry canon_config.h; the ctx (circkit_hip.hip)
 // is seen with its fields, through ck_ctx_impl.h: the canonicalize state is allocated with it.
@@ -17,18 +17,12 @@ namespace {
 
 int ensure_lists(circkit_ctx* c, uint64_t entries, uint64_t segs)
 {
-    if (entries > c->list_cap) {
-        c->list_cap = 0;
-        for (int i = 0; i < N_TIERS + 1; ++i) {
-            if (c->d_lists[i]) { (void)hipFree(c->d_lists[i]); c->d_lists[i] = nullptr; }
-            CK_HIP(c, hipMalloc(&c->d_lists[i], entries * sizeof(uint32_t)));
-        }
-        c->list_cap = entries;
-    }
+    int rc;
+    for (auto& list : c->d_lists)           // (all of one size: a list that is large enough already stays)
+        if ((rc = list.grow(c, entries))) return rc;
     if (segs > c->seg_alloc) {
-        if (c->d_seg_counts) { (void)hipFree(c->d_seg_counts); c->d_seg_counts = nullptr; }
         c->seg_alloc = 0;
-        CK_HIP(c, hipMalloc(&c->d_seg_counts, (N_TIERS + 1) * segs * sizeof(uint32_t)));
+        if ((rc = c->d_seg_counts.grow(c, (N_TIERS + 1) * segs))) return rc;
         c->seg_alloc = segs;
     }
     return CIRCKIT_OK;
@@ -44,123 +38,59 @@ struct Batch {
     uint32_t host_mode, kmode;      // the mode the host has seen or guessed (0: the device decides) / what the kernels get (+ bit 31: guessed)
     bool aux;                       // the rotation index, the strand or the forward-only variant is wanted
 };
-inline const uint32_t* mode_word(const circkit_ctx* c) { return c->d_counters + 5; }
+inline const uint32_t* mode_word(const circkit_ctx* c) { return c->d_counters + CTR_MODE; }
 
-// One build of the streaming kernel.  full: the build this batch is expected to run, one workgroup per list segment
-// (PERSIST = false); otherwise its twin that walks the G virtual workgroups with a small grid, returns at once when the
-// batch is not its own and takes the whole batch when the expectation was wrong.
-template <class CFG, bool HASH, bool AUX, bool ALPHA>
-void launch_stream(circkit_ctx* c, const Batch& b, bool full)
-{
-    const unsigned small = b.G < 2u * N_CU ? b.G : 2u * N_CU;
-    const auto kernel = full ? canon_stream_kernel<CFG, HASH, AUX, false, ALPHA> : canon_stream_kernel<CFG, HASH, AUX, true, ALPHA>;
-    hipLaunchKernelGGL(kernel, dim3(full ? b.G : small), dim3(CFG::WPB * 64), 0, c->stream, b.a, mode_word(c), b.kmode, b.G);
-}
+// The kernels of the front builds, entry for entry of FRONT_BUILDS (canon_plan.h).  A streaming build has two: [1] one workgroup
+// per list segment, for the batch it is expected to own; [0] its PERSIST twin, which walks the G virtual workgroups with a small
+// grid, returns at once when the batch is not its own and takes the whole batch when the expectation was wrong.
+using StreamFn = void (*)(ck::CanonArgs, const uint32_t*, uint32_t, uint32_t);
+using RescueFn = void (*)(ck::CanonArgs, const uint32_t*, uint32_t, uint32_t*, uint32_t*);
+using MixedFn = void (*)(ck::CanonArgs, const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*);
+struct FrontKernel { StreamFn stream[2]; RescueFn rescue; MixedFn mixed; };
+const FrontKernel FRONT_KERNELS[N_FRONT_BUILDS] = {
+#define CK_X(id, CFG, HASH, AUX, ALPHA) { { canon_stream_kernel<CFG, HASH, AUX, true, ALPHA>, canon_stream_kernel<CFG, HASH, AUX, false, ALPHA> }, nullptr, nullptr },
+    CK_STREAM_BUILDS(CK_X)
+#undef CK_X
+#define CK_X(id, HASH, AUX, ALPHA) { {}, canon_rescue_kernel<HASH, AUX, ALPHA>, nullptr },
+    CK_RESCUE_BUILDS(CK_X)
+#undef CK_X
+#define CK_X(id, KERNEL, NM, HASH) { {}, nullptr, KERNEL },
+    CK_MIXED_BUILDS(CK_X)
+#undef CK_X
+};
 
-// Stage 1: the streaming kernel over every record; what it cannot take goes down the LDS tiers.
-// Three builds of it: canonical bytes only (the headline), + fused XXH3 (uniq), and the general one for callers that also
-// want the rotation index / strand or the forward-only variant (lmsr); each for ROWS = 1 and ROWS = 2.  The host's answer
-// launches exactly one of the two; a device-side decision launches both, full-size where the previous batch's mode says it
-// will run.
-void stage_stream(circkit_ctx* c, Batch& b, bool device_decides)
+// Stages 1 to 3, the front of a batch: the streaming kernel over every record (what it cannot take goes down the LDS tiers), the
+// rescue pass over its leftovers, segment for segment into the next list, and -- mode 3 -- a mixed-length kernel over every
+// record in its place (same lists, same segments).  Which builds are launched, and with which grid, is canon_front_plan's.
+void stage_front(circkit_ctx* c, Batch& b, bool device_decides)
 {
     ck::CanonArgs& a = b.a;
-    const uint32_t host_mode = b.host_mode;
-    const bool aux = b.aux, hash = a.out_hash != nullptr;
-    a.list = nullptr; a.list_count = nullptr;
-    a.defer_list = c->d_lists[0]; a.defer_count = c->d_seg_counts; a.out_seg_cap = b.seg_cap;
-    a.slice_dw = 0;
+    const bool hash = a.out_hash != nullptr;
     if (device_decides) {
         const uint64_t ns = count_samples(a.n_records);
         const unsigned cgrid = (unsigned)((ns + 1023) / 1024 < 128 ? (ns + 1023) / 1024 : 128);
-        hipLaunchKernelGGL(stream_count_kernel, dim3(cgrid), dim3(1024), 0, c->stream, a.bytes, a.offsets, a.n_records, c->d_counters + 8, c->d_counters + 5, c->d_counters, (hash && !aux) ? 1u : 0u);
+        hipLaunchKernelGGL(stream_count_kernel, dim3(cgrid), dim3(1024), 0, c->stream, a.bytes, a.offsets, a.n_records, c->d_counters + CTR_COUNT, c->d_counters + CTR_MODE, (uint32_t*)c->d_counters, (hash && !b.aux) ? 1u : 0u);
     }
-    // the mode of whichever earlier batch last reported: a hint for the grid sizes, nothing else
-    const uint32_t seen = *c->h_mode;
-    const uint32_t expect = host_mode ? host_mode & 3 : ((seen & 3) ? seen & 3 : 1u);
-    // (rows, alphabet) builds: ROWS = 1 lean, ROWS = 1 with the 4-bit routine, ROWS = 2.  The host's answer launches
-    // exactly one; a device-side decision launches all three, full-size where the previous batch's mode says it will run
-    const uint32_t expect_alpha = host_mode ? host_mode & MODE_ALPHA : seen & MODE_ALPHA;
-    for (uint32_t rows = 1; rows <= 2; ++rows) {
-        if (host_mode && (host_mode & 3) != rows) continue;
-        for (uint32_t alpha = 0; alpha <= (rows == 1 && !aux ? 1u : 0u); ++alpha) {
-            if (host_mode && rows == 1 && !aux && ((host_mode & MODE_ALPHA) != 0) != (alpha != 0)) continue;
-            const bool full = expect == rows && (rows != 1 || aux || (expect_alpha != 0) == (alpha != 0));
-            if (rows == 1) {
-                if (aux) launch_stream<StreamCAux, true, true, false>(c, b, full);
-                else if (hash) { if (alpha) launch_stream<StreamCH, true, false, true>(c, b, full); else launch_stream<StreamCHP, true, false, false>(c, b, full); }
-                else if (alpha) launch_stream<StreamCA, false, false, true>(c, b, full);
-                else {
-                    // bytes only, pure ACGT: one record per wave, or -- MODE_SHORT -- two; the host's answer launches one of the builds,
-                    // a device-side decision both (the one the previous batch did not use with the small grid)
-                    const bool expect_short = ((host_mode ? host_mode : seen) & MODE_SHORT) != 0;
-                    for (int sh = 0; sh < 2; ++sh) {
-                        if (host_mode && (sh != 0) != expect_short) continue;
-                        const bool full_sh = full && (sh != 0) == expect_short;
-                        if (sh) launch_stream<StreamCHP, false, false, false>(c, b, full_sh);
-                        else launch_stream<StreamC, false, false, false>(c, b, full_sh);
-                    }
-                }
-            } else {
-                if (aux) launch_stream<StreamCAux2, true, true, false>(c, b, full);
-                else if (hash) launch_stream<StreamC2, true, false, false>(c, b, full);
-                else launch_stream<StreamC2, false, false, false>(c, b, full);
-            }
+    // (the mode of whichever earlier batch last reported, straight from pinned host memory: a hint for the grid sizes, nothing else)
+    const FrontPlan plan = canon_front_plan(b.aux, hash, b.host_mode, c->h_mode[HM_MODE], b.G, b.nseg);
+    for (int i = 0; i < plan.n; ++i) {
+        const FrontLaunch& e = plan.e[i];
+        const FrontBuild& fb = FRONT_BUILDS[e.build];
+        const FrontKernel& k = FRONT_KERNELS[e.build];
+        const dim3 grid(e.grid), block(fb.block);
+        if (fb.stage == FRONT_STREAM) { a.list = nullptr; a.list_count = nullptr; }
+        else {
+            a.list = c->d_lists[0]; a.list_count = c->d_seg_counts;
+            a.in_nseg = b.nseg; a.in_seg_cap = b.seg_cap; a.segs_per_block = 1;
         }
-    }
-}
-
-// Stage 2: the rescue pass over the streaming kernel's leftovers, segment for segment into the next list.
-void stage_rescue(circkit_ctx* c, Batch& b)
-{
-    ck::CanonArgs& a = b.a;
-    const uint32_t host_mode = b.host_mode;
-    const unsigned grid = b.nseg < (unsigned)N_CU * CK_RESCUE_BPC ? b.nseg : (unsigned)N_CU * CK_RESCUE_BPC;
-    a.list = c->d_lists[0]; a.list_count = c->d_seg_counts;
-    a.in_nseg = b.nseg; a.in_seg_cap = b.seg_cap; a.segs_per_block = 1;
-    a.defer_list = c->d_lists[1]; a.defer_count = c->d_seg_counts + c->seg_alloc; a.out_seg_cap = b.seg_cap;
-    // (the batch's mode goes straight into pinned host memory, c->d_mode: no copy-back, no event)
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c->stream, a, mode_word(c), b.kmode, c->d_mode, c->d_counters + 1); };
-    // both alphabets' builds unless the host has decided; the one the mode does not name returns at once
-    const bool mixed_has_it = host_mode && !b.aux && (host_mode & 3) == 3;
-    const bool lean = (!host_mode || !(host_mode & MODE_ALPHA)) && !mixed_has_it, alpha = (!host_mode || (host_mode & MODE_ALPHA)) && !mixed_has_it;
-    if (b.aux) launch(canon_rescue_kernel<true, true, false>);
-    else if (a.out_hash) {
-        if (lean) launch(canon_rescue_kernel<true, false, false>);
-        if (alpha) launch(canon_rescue_kernel<true, false, true>);
-    } else {
-        if (lean) launch(canon_rescue_kernel<false, false, false>);
-        if (alpha) launch(canon_rescue_kernel<false, false, true>);
-    }
-}
-
-// Stage 3, mode 3: canon_mixed_kernel takes every record (the rescue pass stood out); same lists, same segments.  Both
-// alphabets' builds unless the host has decided; one workgroup per segment for the build the previous batch used,
-// a small walking grid for the other (it returns at once unless the expectation was wrong).
-void stage_mixed(circkit_ctx* c, Batch& b)
-{
-    ck::CanonArgs& a = b.a;
-    const uint32_t host_mode = b.host_mode;
-    if (b.aux || (host_mode && (host_mode & 3) != 3)) return;
-    const bool hash = a.out_hash != nullptr;
-    const unsigned nseg = b.nseg;
-    const uint32_t seen = *c->h_mode;
-    const unsigned walking = nseg < (unsigned)N_CU * CK_RESCUE_BPC ? nseg : (unsigned)N_CU * CK_RESCUE_BPC;
-    for (uint32_t nm = 0; nm < 2; ++nm) {
-        if (host_mode && ((host_mode & MODE_ALPHA) != 0) != (nm != 0)) continue;
-        const bool expected = host_mode ? true : ((seen & 3) == 3 && ((seen & MODE_ALPHA) != 0) == (nm != 0));
-        // N builds: a resident grid (five workgroups per CU) fed by ticket; pure builds: one workgroup per segment
-        const unsigned resident = (unsigned)N_CU * (20u / (unsigned)mixed_wpb(true, false));      // (20 waves per CU by LDS)
-        const unsigned full = nm ? (nseg < resident ? nseg : resident) : nseg;
-        const unsigned grid = expected ? full : walking;
-        uint32_t* ticket = nm ? c->d_counters + 16 : nullptr;   // [16], [17]: self-zeroing
-        // the N build keeps one N bit per symbol (and lean_resolve_n's candidates) behind the strand: half as much again, so
-        // that a 20 kb record of config 4 fits a slice (n / 16 + n / 32 + 24 dwords) -- five workgroups = 20 waves per CU
-        a.slice_dw = nm ? CK_MIXED_N_SLICE : TIER_DW[0];
-        const int mwpb = nm ? mixed_wpb(true, hash) : (hash ? mixed_wpb(false, true) : mixed_wpb(false, false));
-        const size_t shmem = ((size_t)mwpb * a.slice_dw + 4 + ck::FAST_LUT_DW + ck::LEAN_LUTN_DW + (hash ? ck::LEAN_HASH_TABLE_DW : 0)) * 4;
-        const auto kernel = hash ? (nm ? canon_mixed_nh_kernel : canon_mixed_h_kernel) : (nm ? canon_mixed_n_kernel : canon_mixed_kernel);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * mwpb), shmem, c->stream, a, mode_word(c), b.kmode, c->d_mode, c->d_counters + 1, ticket);
+        const int out = fb.stage == FRONT_STREAM ? 0 : 1;
+        a.defer_list = c->d_lists[out]; a.defer_count = c->d_seg_counts + out * c->seg_alloc; a.out_seg_cap = b.seg_cap;
+        a.slice_dw = fb.slice_dw;
+        // (the batch's mode goes straight into pinned host memory, c->d_mode: no copy-back, no event)
+        if (fb.stage == FRONT_STREAM) hipLaunchKernelGGL(k.stream[e.full], grid, block, 0, c->stream, a, mode_word(c), b.kmode, b.G);
+        else if (fb.stage == FRONT_RESCUE) hipLaunchKernelGGL(k.rescue, grid, block, 0, c->stream, a, mode_word(c), b.kmode, c->d_mode + HM_MODE, c->d_counters + CTR_TIERS_BUSY);
+        else hipLaunchKernelGGL(k.mixed, grid, block, fb.lds, c->stream, a, mode_word(c), b.kmode, c->d_mode + HM_MODE, c->d_counters + CTR_TIERS_BUSY,
+                                fb.alpha ? c->d_counters + CTR_MIXED_TICKET : (uint32_t*)nullptr);
     }
 }
 
@@ -206,7 +136,7 @@ void dump_stage_a_input(circkit_ctx* c, const Batch& b)
 void stage_tiers(circkit_ctx* c, Batch& b)
 {
     ck::CanonArgs& a = b.a;
-    const bool tiers_idle = c->h_mode[1] == 1;       // the previous batch's tiers found (next to) nothing: small grids for this one
+    const bool tiers_idle = c->h_mode[HM_TIERS] == 1;       // the previous batch's tiers found (next to) nothing: small grids for this one
     // (What the idle tiers cost live, measured by not launching them: 82 us of the 3.70 ms headline step, 116 us of uniq's
     // 5.26; with the parallel look at the counts in canon_kernel ~40 us remain -- five dependent launches.)
     for (int t = 0; t < BATCH_TIERS; ++t) {
@@ -227,7 +157,7 @@ void stage_tiers(circkit_ctx* c, Batch& b)
         // `grid` virtual workgroups; launched: a few times what is resident at once (dispatch order balances the rest)
         const unsigned bpc = tiers_idle ? CK_TIER_BPC_IDLE : CK_TIER_BPC;
         const unsigned launched = grid < (unsigned)N_CU * bpc ? grid : (unsigned)N_CU * bpc;
-        if (last) hipLaunchKernelGGL(canon_team_kernel, dim3(launched), dim3(TEAM_WAVES * 64), (TEAM_WAVES * TEAM_SLICE_DW + TIER_EXTRA_DW) * 4, c->stream, a, grid, c->d_counters);
+        if (last) hipLaunchKernelGGL(canon_team_kernel, dim3(launched), dim3(TEAM_WAVES * 64), (TEAM_WAVES * TEAM_SLICE_DW + TIER_EXTRA_DW) * 4, c->stream, a, grid, c->d_counters + CTR_PASSED_ON);
         else hipLaunchKernelGGL((tiers_idle ? canon_kernel<4, false> : canon_kernel<4, true>), dim3(launched), dim3(256), (4 * a.slice_dw + TIER_EXTRA_DW) * 4, c->stream, a, grid, (uint32_t*)nullptr);
         b.nseg = grid;
         b.seg_cap = spb * seg_cap;
@@ -258,8 +188,8 @@ void stage_global(circkit_ctx* c, Batch& b)
     a2.in_nseg = w1; a2.in_seg_cap = spb1 * seg_cap; a2.segs_per_block = w1;
     a2.defer_list = nullptr; a2.defer_count = nullptr; a2.out_seg_cap = 0;
     a2.slice_dw = (uint32_t)(cap_dw < 0xFFFFFFFFull ? cap_dw : 0xFFFFFFFFull);
-    hipLaunchKernelGGL(canon_global_kernel, dim3(w1), dim3(TEAM_WAVES * 64), 0, c->stream, a, a2, (uint32_t*)c->d_gscratch.p, c->d_counters + 2, (const uint32_t*)c->d_counters,
-                       (const uint32_t*)(c->d_counters + 1), c->d_mode + 1);
+    hipLaunchKernelGGL(canon_global_kernel, dim3(w1), dim3(TEAM_WAVES * 64), 0, c->stream, a, a2, (uint32_t*)c->d_gscratch.p, c->d_counters + CTR_GLOBAL_TICKET,
+                       (const uint32_t*)(c->d_counters + CTR_PASSED_ON), (const uint32_t*)(c->d_counters + CTR_TIERS_BUSY), c->d_mode + HM_TIERS);
 }
 
 // Stage 6: the XXH3 of the records whose hash was not fused: from their canonical bytes, or (hash-only batch) from the input
@@ -270,7 +200,7 @@ void stage_leftover_xxh3(circkit_ctx* c, const Batch& b)
     if (!a.out_hash) return;
     const uint8_t* src = a.out_view ? a.bytes : a.out_bytes;
     hipLaunchKernelGGL(xxh3_kernel, dim3(b.G < 2048u ? b.G : 2048u), dim3(256), 0, c->stream, src, a.offsets, a.n_records, a.out_hash, (const uint8_t*)c->d_hashed,
-                       (const uint32_t*)a.out_view, (const uint8_t*)(a.out_view ? c->d_comp : nullptr));
+                       (const uint32_t*)a.out_view, a.out_view ? (const uint8_t*)c->d_comp : nullptr);
 }
 
 // Enqueues one batch: every kernel, nothing else -- no host-side follow-up is needed once the stream has run them
@@ -295,7 +225,7 @@ int launch_canon(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offse
     uint32_t guess_flag = 0;
     if (device_decides) {
         static const bool no_guess = getenv("CIRCKIT_NO_MODE_GUESS") != nullptr;
-        const uint32_t seen = *c->h_mode & 15u;
+        const uint32_t seen = c->h_mode[HM_MODE] & 15u;
         if (!no_guess && (seen & 3u) && seen == c->mode_seen) { host_mode = seen; guess_flag = 0x80000000u; }
         c->mode_seen = seen;
         static const bool dbg = getenv("CIRCKIT_DEBUG_MODE_GUESS") != nullptr;
@@ -319,24 +249,20 @@ int launch_canon(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offse
         if (n > c->d_hashed.cap && (rc = c->d_hashed.grow(c, n + n / 8 + 64))) return rc;
         CK_HIP(c, hipMemsetAsync(c->d_hashed, 0, n, c->stream));
     }
-    // d_counters: [0] records the last LDS tier passed on, [2] arrival ticket of the global-scratch kernel (leaves it zero),
-    // [3] records nothing could take,
-    // [5] the batch's mode (device-side decision), [8..10] the count kernel's counters and ticket (it leaves them zero).
-    // A device-side decision zeroes [0] and [3] in its count kernel; the host-side one with a memset.
-    // (keep_status: a later part of a host batch -- counters[3], the records nothing could take, adds up over the parts)
-    if (!device_decides) CK_HIP(c, hipMemsetAsync(c->d_counters, 0, (keep_status ? 3 : 4) * sizeof(uint32_t), c->stream));
+    // d_counters (canon_plan.h CounterWord): a device-side decision zeroes the words a batch starts from in its count kernel, the
+    // host-side one with a memset.
+    // (keep_status: a later part of a host batch -- CTR_UNPROCESSED, the records nothing could take, adds up over the parts)
+    if (!device_decides) CK_HIP(c, hipMemsetAsync(c->d_counters, 0, (keep_status ? CTR_UNPROCESSED : CTR_ZEROED_PER_BATCH) * sizeof(uint32_t), c->stream));
     CK_HIP(c, hipEventRecord(c->ev0, c->stream));
     Batch b{};
     ck::CanonArgs& a = b.a;
     a.bytes = d_bytes; a.offsets = d_offsets; a.n_records = n;
     a.out_bytes = d_out; a.out_index = d_idx; a.out_strand = d_strand; a.out_hash = d_hash; a.hashed = c->d_hashed; a.out_view = view;
-    a.comp_lut = c->d_comp; a.status = c->d_counters + 3; a.flags = flags;
+    a.comp_lut = c->d_comp; a.status = c->d_counters + CTR_UNPROCESSED; a.flags = flags;
     a.all_seg_cap = g.all_cap; a.taper_seg0 = g.taper_seg0; a.taper_log2 = g.taper_log2;
     b.nseg = g.G; b.seg_cap = g.cap; b.G = g.G;
     b.host_mode = host_mode; b.kmode = host_mode | guess_flag; b.aux = aux;
-    stage_stream(c, b, device_decides);
-    stage_rescue(c, b);
-    stage_mixed(c, b);
+    stage_front(c, b, device_decides);
 #ifdef CK_DEBUG_DUMP
     dump_stage_a_input(c, b);
 #endif
@@ -358,8 +284,8 @@ int launch_single(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs
     ck::CanonArgs a{};
     a.bytes = d_bytes; a.offsets = d_offsets; a.n_records = 1;
     a.out_bytes = d_out; a.out_index = d_idx; a.out_strand = d_strand; a.out_hash = nullptr; a.hashed = nullptr;
-    a.comp_lut = c->d_comp; a.status = c->d_counters + 3; a.flags = flags;
-    CK_HIP(c, hipMemsetAsync(c->d_counters + 3, 0, sizeof(uint32_t), c->stream));
+    a.comp_lut = c->d_comp; a.status = c->d_counters + CTR_UNPROCESSED; a.flags = flags;
+    CK_HIP(c, hipMemsetAsync(c->d_counters + CTR_UNPROCESSED, 0, sizeof(uint32_t), c->stream));
     const uint64_t need = worst_case_dw(len);
     int t = 0;
     while (t < N_TIERS && TIER_DW[t] < need) ++t;
@@ -378,33 +304,17 @@ int launch_single(circkit_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs
     return CIRCKIT_OK;
 }
 
-template <class T>
-int grow(circkit_ctx* c, T*& p, uint64_t want_elems)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
-    CK_HIP(c, hipMalloc(&p, want_elems * sizeof(T)));
-    return CIRCKIT_OK;
-}
-
+// (the buffer grown last answers for its group: after a failed allocation it has not grown, and the group is grown again)
 int ensure_staging(circkit_ctx* c, uint64_t bytes, uint64_t recs)
 {
-    if (bytes + 64 > c->cap_bytes) {
+    int rc;
+    if (bytes + 64 > c->d_out.cap) {
         const uint64_t nb = bytes + bytes / 8 + 4096;
-        c->cap_bytes = 0;
-        int rc;
-        if ((rc = grow(c, c->d_in, nb))) return rc;
-        if ((rc = grow(c, c->d_out, nb))) return rc;
-        c->cap_bytes = nb;
+        if ((rc = c->d_in.grow(c, nb)) || (rc = c->d_out.grow(c, nb))) return rc;
     }
-    if (recs + 1 > c->cap_rec) {
+    if (recs + 1 > c->d_hash.cap) {
         const uint64_t nr = recs + recs / 8 + 1024;
-        c->cap_rec = 0;
-        int rc;
-        if ((rc = grow(c, c->d_off, nr))) return rc;
-        if ((rc = grow(c, c->d_idx, nr))) return rc;
-        if ((rc = grow(c, c->d_strand, nr))) return rc;
-        if ((rc = grow(c, c->d_hash, nr))) return rc;
-        c->cap_rec = nr;
+        if ((rc = c->d_off.grow(c, nr)) || (rc = c->d_idx.grow(c, nr)) || (rc = c->d_strand.grow(c, nr)) || (rc = c->d_hash.grow(c, nr))) return rc;
     }
     return CIRCKIT_OK;
 }
@@ -420,7 +330,6 @@ int host_batch(circkit_ctx* c, const uint8_t* bytes, const uint64_t* offsets, ui
     if (!c) return CIRCKIT_ERR_INVALID_ARG;
     const int rc = host_batch_enqueue(c, bytes, offsets, n, out, idx, strand, hash, flags);
     if (rc != CIRCKIT_OK) {
-        if (c->s_in) (void)hipStreamSynchronize(c->s_in);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         if (c->s_out) (void)hipStreamSynchronize(c->s_out);
     }
@@ -466,7 +375,7 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
         if (strand) CK_HIP(c, hipMemcpyAsync(strand, c->d_strand, n, hipMemcpyDeviceToHost, c->stream));
         if (hash) CK_HIP(c, hipMemcpyAsync(hash, c->d_hash, n * 8, hipMemcpyDeviceToHost, c->stream));
         uint32_t unprocessed = 0;
-        CK_HIP(c, hipMemcpyAsync(&unprocessed, c->d_counters + 3, 4, hipMemcpyDeviceToHost, c->stream));
+        CK_HIP(c, hipMemcpyAsync(&unprocessed, c->d_counters + CTR_UNPROCESSED, 4, hipMemcpyDeviceToHost, c->stream));
         CK_HIP(c, hipStreamSynchronize(c->stream));
         if (unprocessed) return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "%u record(s) could not be processed", unprocessed);
         return CIRCKIT_OK;
@@ -494,31 +403,17 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     // The copy-in rides the ctx stream itself, part k + 1 queued behind part k's kernels (a few hundred microseconds next to the
     // milliseconds of a part's copy); the copy-out has a stream of the ctx's own, at a priority of its own (the runtime keeps
     // a separate set of hardware queues per priority: no queue shared with the ctx stream or any default-priority stream).
-    // With a plain copy-in and a plain copy-out stream -- round 3's first arrangement -- the two directions of a call
-    // overlapped or took turns (1 GB: 24.8 or 38-40 ms) depending on how many streams the process had made before: one extra
-    // stream ahead of the ctx was slow in 2 runs of 2 (tools/probe_stream_luck.py), and so were bench.py's `uniq` processes.
-    // In this arrangement 130 fresh processes in the same probes were fast but one -- which had run straight behind a process
-    // that had just released tens of GB of device memory: for some seconds after such an exit the copy engines are busy with
-    // the driver's handling of that memory and the directions of every process's copies take turns
-    // (tools/probe_after_big_process.sh); nothing a library can do about, bench.py's end-to-end leg waits it out.  Moving the bytes out by a copy kernel that stores across
-    // the link instead of the DMA engine: 28 ms, and it took turns as well when it did.
-    // CIRCKIT_HOST_BATCH_PLAIN_STREAMS=1: the first arrangement, for comparison.
-    static const bool plain_streams = getenv("CIRCKIT_HOST_BATCH_PLAIN_STREAMS") != nullptr;
-    const bool inline_h2d = !plain_streams;
+    // With a plain copy-in and a plain copy-out stream -- round 3's first arrangement, dropped since -- the two directions of a
+    // call overlapped or took turns (1 GB: 24.8 or 38-40 ms) depending on how many streams the process had made before.  In this
+    // arrangement only a process that runs straight behind one that has just released tens of GB of device memory is slow: for
+    // some seconds the copy engines are busy with the driver's handling of that memory (tools/probe_after_big_process.sh);
+    // bench.py's end-to-end leg waits it out.  A copy kernel that stores across the link instead of the DMA engine: 28 ms.
     if (!c->s_out) {
-        if (plain_streams) {
-            CK_HIP(c, hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
-            CK_HIP(c, hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
-        } else {
-            int prio_least = 0, prio_greatest = 0;
-            CK_HIP(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-            CK_HIP(c, hipStreamCreateWithPriority(&c->s_out, hipStreamNonBlocking, prio_greatest));
-        }
+        int prio_least = 0, prio_greatest = 0;
+        CK_HIP(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+        CK_HIP(c, hipStreamCreateWithPriority(&c->s_out, hipStreamNonBlocking, prio_greatest));
         CK_HIP(c, hipEventCreateWithFlags(&c->ev_head, hipEventDisableTiming));
-        for (int k = 0; k < circkit_ctx::MAX_PARTS; ++k) {
-            CK_HIP(c, hipEventCreateWithFlags(&c->ev_in[k], hipEventDisableTiming));
-            CK_HIP(c, hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming));
-        }
+        for (hipEvent_t& e : c->ev_done) CK_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     // part boundaries: record indices, cut where the payload passes k / parts of its bytes
     uint64_t cut[circkit_ctx::MAX_PARTS + 1];
@@ -532,31 +427,26 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     }
     // whatever the caller has queued on the ctx stream comes first; the offsets go with the first part
     CK_HIP(c, hipEventRecord(c->ev_head, c->stream));
-    if (!inline_h2d) CK_HIP(c, hipStreamWaitEvent(c->s_in, c->ev_head, 0));
     // (through a page-locked copy of them: from the caller's pageable array the runtime stages the copy and the call blocks
     // until it is through -- 0.9 ms of a 64 MB batch's 4.2)
     // The per-record outputs (hash, index, strand: 13 bytes a record) come back the same way: into page-locked staging part by
     // part, to the caller's arrays once at the end -- a copy-out to pageable memory would hold up every part behind it
     // (uniq on 1M x 1 kb: 38.6 ms per call with the hashes going straight to a pageable array, 23.7 without hashes).
-    if (n + 1 > c->h_off_cap) {
-        if (c->h_off) { (void)hipHostFree((void*)c->h_off); c->h_off = nullptr; c->h_off_cap = 0; }
-        const uint64_t cap = n + 1 + (n + 1) / 8 + 1024;
-        CK_HIP(c, hipHostMalloc((void**)&c->h_off, cap * (8 + 8 + 4 + 1), hipHostMallocDefault));
-        c->h_off_cap = cap;
-    }
-    uint64_t* const st_hash = c->h_off + c->h_off_cap;
-    uint32_t* const st_idx = (uint32_t*)(st_hash + c->h_off_cap);
-    uint8_t* const st_strand = (uint8_t*)(st_idx + c->h_off_cap);
-    memcpy(c->h_off, offsets, (n + 1) * 8);
-    hipStream_t sin = inline_h2d ? c->stream : c->s_in;
-    CK_HIP(c, hipMemcpyAsync(c->d_off, c->h_off, (n + 1) * 8, hipMemcpyHostToDevice, sin));
+    constexpr uint64_t PER_REC = 8 + 8 + 4 + 1;           // offset, hash, index, strand
+    if ((n + 1) * PER_REC > c->h_stage.cap && (rc = c->h_stage.grow(c, (n + 1 + (n + 1) / 8 + 1024) * PER_REC))) return rc;
+    const uint64_t st_recs = c->h_stage.cap / PER_REC;
+    uint64_t* const st_off = (uint64_t*)c->h_stage.p;
+    uint64_t* const st_hash = st_off + st_recs;
+    uint32_t* const st_idx = (uint32_t*)(st_hash + st_recs);
+    uint8_t* const st_strand = (uint8_t*)(st_idx + st_recs);
+    memcpy(st_off, offsets, (n + 1) * 8);
+    CK_HIP(c, hipMemcpyAsync(c->d_off, st_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     auto copy_in = [&](int k) -> int {
         const uint64_t b0 = offsets[cut[k]], b1 = offsets[cut[k + 1]];
-        if (b1 > b0) CK_HIP(c, hipMemcpyAsync(c->d_in + b0, bytes + b0, b1 - b0, hipMemcpyHostToDevice, sin));
-        if (!inline_h2d) CK_HIP(c, hipEventRecord(c->ev_in[k], sin));
+        if (b1 > b0) CK_HIP(c, hipMemcpyAsync(c->d_in + b0, bytes + b0, b1 - b0, hipMemcpyHostToDevice, c->stream));
         return CIRCKIT_OK;
     };
-    for (int k = 0; k < (inline_h2d ? 1 : parts); ++k) if ((rc = copy_in(k))) return rc;
+    if ((rc = copy_in(0))) return rc;
     dbg_lap("enqueue copy-in");
     // ...and, while the first part is on its way, samples the content like stream_count_kernel does (a byte outside ACGT in
     // the first 1008 of a sampled record) -- on an eighth of that kernel's sample: the rule asks whether a sixteenth of the
@@ -575,16 +465,15 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     }
     const uint32_t host_mode = batch_mode_of(two_word, longer, n, bad, nc, shorter, hash != nullptr && !idx && !strand && !(flags & ck::CK_FLAG_FWD_ONLY));
     dbg_lap("content sample");
-    volatile uint32_t* unprocessed = c->h_mode + 4;                       // (pinned)
+    volatile uint32_t* unprocessed = c->h_mode + HM_UNPROCESSED;          // (pinned)
     for (int k = 0; k < parts; ++k) {
         const uint64_t r0 = cut[k], nk = cut[k + 1] - r0, b0 = offsets[r0], b1 = offsets[cut[k + 1]];
-        if (!inline_h2d) CK_HIP(c, hipStreamWaitEvent(c->stream, c->ev_in[k], 0));
         rc = launch_canon(c, c->d_in, c->d_off + r0, nk, need_bytes ? c->d_out : nullptr, idx ? c->d_idx + r0 : nullptr,
                           strand ? c->d_strand + r0 : nullptr, hash ? c->d_hash + r0 : nullptr, flags, host_mode, k > 0);
         if (rc) return rc;                                  // (host_batch drains the streams)
         CK_HIP(c, hipEventRecord(c->ev_done[k], c->stream));
         CK_HIP(c, hipStreamWaitEvent(c->s_out, c->ev_done[k], 0));
-        if (inline_h2d && k + 1 < parts && (rc = copy_in(k + 1))) return rc;
+        if (k + 1 < parts && (rc = copy_in(k + 1))) return rc;
         if (out && b1 > b0) CK_HIP(c, hipMemcpyAsync(out + b0, c->d_out + b0, b1 - b0, hipMemcpyDeviceToHost, c->s_out));
         if (idx) CK_HIP(c, hipMemcpyAsync(st_idx + r0, c->d_idx + r0, nk * 4, hipMemcpyDeviceToHost, c->s_out));
         if (strand) CK_HIP(c, hipMemcpyAsync(st_strand + r0, c->d_strand + r0, nk, hipMemcpyDeviceToHost, c->s_out));
@@ -593,7 +482,7 @@ int host_batch_enqueue(circkit_ctx* c, const uint8_t* bytes, const uint64_t* off
     // the count of records nothing could take, added up over the parts (only part 0's launch zeroes it): read once, behind the
     // last part -- a copy of it per part made every part's kernels wait for the copy-out two parts back
     unprocessed[0] = 0;
-    CK_HIP(c, hipMemcpyAsync((void*)unprocessed, c->d_counters + 3, 4, hipMemcpyDeviceToHost, c->s_out));
+    CK_HIP(c, hipMemcpyAsync((void*)unprocessed, c->d_counters + CTR_UNPROCESSED, 4, hipMemcpyDeviceToHost, c->s_out));
     dbg_lap("enqueue parts");
     CK_HIP(c, hipStreamSynchronize(c->s_out));
     dbg_lap("sync copy-out");
@@ -638,7 +527,7 @@ int circkit_ctx_batch_status(circkit_ctx* c, uint32_t* n_unprocessed)
     if (!c || !n_unprocessed) return CIRCKIT_ERR_INVALID_ARG;
     CK_HIP(c, hipSetDevice(c->device));
     *n_unprocessed = 0;
-    CK_HIP(c, hipMemcpyAsync(n_unprocessed, c->d_counters + 3, 4, hipMemcpyDeviceToHost, c->stream));
+    CK_HIP(c, hipMemcpyAsync(n_unprocessed, c->d_counters + CTR_UNPROCESSED, 4, hipMemcpyDeviceToHost, c->stream));
     CK_HIP(c, hipStreamSynchronize(c->stream));
     if (*n_unprocessed)
         return ck_fail(c, CIRCKIT_ERR_TOO_LONG, "%u record(s) were not processed: longer than the long-record scratch (%llu MiB, "
@@ -661,7 +550,7 @@ int circkit_ctx_last_batch_mode(circkit_ctx* c, uint32_t* mode)
     if (!c || !mode) return CIRCKIT_ERR_INVALID_ARG;
     CK_HIP(c, hipSetDevice(c->device));
     CK_HIP(c, hipStreamSynchronize(c->stream));
-    *mode = *c->h_mode & 3;
+    *mode = c->h_mode[HM_MODE] & 3;
     return CIRCKIT_OK;
 }
 
@@ -776,7 +665,7 @@ int circkit_debug_poison_count(circkit_ctx* c, uint32_t* n)
     if (!c || !n) return CIRCKIT_ERR_INVALID_ARG;
     CK_HIP(c, hipSetDevice(c->device));
     CK_HIP(c, hipStreamSynchronize(c->stream));
-    CK_HIP(c, hipMemcpy(n, c->d_counters + 12, 4, hipMemcpyDeviceToHost));
+    CK_HIP(c, hipMemcpy(n, c->d_counters + CTR_POISON, 4, hipMemcpyDeviceToHost));
     return CIRCKIT_OK;
 }
 #endif

@@ -46,12 +46,12 @@ int circkit_ctx_create(int device, circkit_ctx** out)
     CK_HIP(c, hipEventCreate(&c->ev0));
     CK_HIP(c, hipEventCreate(&c->ev1));
     CK_HIP(c, hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
-    CK_HIP(c, hipHostMalloc((void**)&c->h_mode, 256, hipHostMallocMapped));      // [0] mode, [1] tiers-busy flag, [4 .. 4 + MAX_PARTS) host_batch's per-part status
-    c->h_mode[0] = 0; c->h_mode[1] = 0;
-    CK_HIP(c, hipHostGetDevicePointer((void**)&c->d_mode, (void*)c->h_mode, 0));
-    CK_HIP(c, hipMalloc(&c->d_comp, 256));
-    CK_HIP(c, hipMalloc(&c->d_counters, 32 * sizeof(uint32_t)));
-    CK_HIP(c, hipMemset(c->d_counters, 0, 32 * sizeof(uint32_t)));
+    int rc;
+    if ((rc = c->h_mode.grow(c, 64, hipHostMallocMapped))) return rc;            // (canon_plan.h HostWord)
+    c->h_mode[HM_MODE] = 0; c->h_mode[HM_TIERS] = 0;
+    CK_HIP(c, hipHostGetDevicePointer((void**)&c->d_mode, (void*)c->h_mode.p, 0));
+    if ((rc = c->d_comp.grow(c, 256)) || (rc = c->d_counters.grow(c, CTR_WORDS))) return rc;
+    CK_HIP(c, hipMemset(c->d_counters, 0, CTR_WORDS * sizeof(uint32_t)));
     uint8_t comp[256];
     for (int v = 0; v < 256; ++v) comp[v] = (uint8_t)v;
     // bio 1.3.1 alphabets::dna complement table (call site lib/src/canonicalize.rs:56)
@@ -66,22 +66,15 @@ int circkit_ctx_destroy(circkit_ctx* c)
     if (!c) return CIRCKIT_OK;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    void* ptrs[] = { c->d_comp, c->d_counters, c->d_seg_counts, c->d_in, c->d_out, c->d_strand, c->d_off, c->d_idx, c->d_hash };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (uint32_t* p : c->d_lists) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
     if (c->ev_head) (void)hipEventDestroy(c->ev_head);
-    for (hipEvent_t e : c->ev_in) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_done) if (e) (void)hipEventDestroy(e);
-    if (c->s_in) (void)hipStreamDestroy(c->s_in);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
-    if (c->h_mode) (void)hipHostFree((void*)c->h_mode);
-    if (c->h_off) (void)hipHostFree((void*)c->h_off);
     for (auto& u : c->units) if (u.release) u.release(u.p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;                            // (with its ck_bufs)
+    delete c;                            // (with its buffers, device and page-locked)
     return CIRCKIT_OK;
 }
 

@@ -114,6 +114,29 @@ inline uint32_t ck_grid_of(uint64_t work, uint32_t per_block, uint32_t max_grid)
     return (uint32_t)(blocks > max_grid ? max_grid : blocks);
 }
 
+// Page-locked host memory that frees itself, and its capacity: staging the link copies from and into without a bounce, or
+// (flags = hipHostMallocMapped) words a kernel writes and the host reads without waiting.
+template <typename T>
+struct ck_pinned {
+    T* p = nullptr;
+    uint64_t cap = 0;                // elements
+    ck_pinned() = default;
+    ck_pinned(const ck_pinned&) = delete;
+    ck_pinned& operator=(const ck_pinned&) = delete;
+    ~ck_pinned() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipHostFree((void*)p); p = nullptr; cap = 0; }
+    // at least `want` elements afterwards (its contents are not kept)
+    int grow(circkit_ctx* c, uint64_t want, unsigned flags = hipHostMallocDefault)
+    {
+        if (want <= cap) return CIRCKIT_OK;
+        release();
+        CK_HIP(c, hipHostMalloc((void**)&p, want * sizeof(T), flags));
+        cap = want;
+        return CIRCKIT_OK;
+    }
+};
+
 // The totals of a unit's most recent call: a few 64-bit words that the kernels write in device memory, and the same words in
 // page-locked host memory, valid once the ctx stream has run past the copy.  How many words, and what they mean, is the unit's.
 struct ck_totals {

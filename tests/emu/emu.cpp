@@ -235,6 +235,7 @@ extern "C" void emu_set_schedule(const char* name)
 #include "../../circkit_amd/csrc/canon_mixed.h"
 #include "../../circkit_amd/csrc/xxh3_core.h"
 #include "../../circkit_amd/csrc/canon_config.h"
+#include "../../circkit_amd/csrc/canon_plan.h"
 
 namespace {
 struct Launch { ck::CanonArgs a; uint32_t* lds; const uint32_t* lut; const uint32_t* lutn = nullptr; const uint32_t* lean_lutn = nullptr; uint32_t* blk_count; uint32_t block, nblocks, wib; bool all_records = false, alpha = false, solo = true, team4 = true; const uint32_t* htab = nullptr; };
@@ -276,16 +277,15 @@ template <class C>
 void stream_body(void* p)       // one fiber of a C::WPB-wave workgroup
 {
     Launch* L = (Launch*)p;
-    // same choice of build as launch_canon()
+    // the builds launch_canon has for geometry C; what each derives from its template arguments is canon_stream_kernel's own
+    // (canon_plan.h StreamBuild): the one-word builds finish XXH3 per record group, two records per wave without the 4-bit
+    // routine run canon_pair.h, one record per half-wave
     const bool aux = L->a.out_index || L->a.out_strand || (L->a.flags & ck::CK_FLAG_FWD_ONLY);
-    if (aux) ck::canon_stream_wave_loop<C, true, true>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks);
+    if (aux) ck::canon_stream_wave_loop<C, true, true, StreamBuild<C, true, true, false>::GH>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks);
     else if (L->a.out_hash) {
-        // the one-record-per-wave, one-word builds finish XXH3 per record group (same condition as canon_stream_kernel: groups of
-        // up to 16 records since round 4)
-        // ...; two records per wave without the 4-bit routine: canon_pair.h, one record per half-wave)
-        constexpr bool GH = C::ROWS == 1 && C::RPW == 1 && C::GROUP <= 16, GHP = C::ROWS == 1 && C::GROUP <= 16;
-        if (L->alpha && C::ROWS == 1) ck::canon_stream_wave_loop<C, true, false, GH, C::ROWS == 1>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks, L->lds + C::LDS_DW);
-        else ck::canon_stream_wave_loop<C, true, false, GHP>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks, L->lds + C::LDS_DW);
+        constexpr bool ALPHA = C::ROWS == 1;        // (the two-word build has no alphabet twin)
+        if (L->alpha && ALPHA) ck::canon_stream_wave_loop<C, true, false, StreamBuild<C, true, false, ALPHA>::GH, ALPHA>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks, L->lds + C::LDS_DW);
+        else ck::canon_stream_wave_loop<C, true, false, StreamBuild<C, true, false, false>::GH>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks, L->lds + C::LDS_DW);
     }
     else if (L->alpha && C::ROWS == 1) ck::canon_stream_wave_loop<C, false, false, false, C::ROWS == 1>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks);
     else ck::canon_stream_wave_loop<C, false, false>(L->a, L->lut, L->lds, L->blk_count, L->block, L->nblocks, L->lds + C::LDS_DW);     // (two records per wave: the pair build's scratch)
@@ -511,4 +511,32 @@ extern "C" void emu_batch_geometry(uint64_t n, uint64_t per_step, uint32_t out[5
     if (per_step < 2) per_step = per_step ? StreamCAux::GROUP : StreamC::GROUP;
     const BatchGeometry g = batch_geometry(n, per_step);
     out[0] = g.G; out[1] = g.cap; out[2] = g.all_cap; out[3] = g.taper_seg0; out[4] = g.taper_log2;
+}
+
+// canon_plan.h, as the kernels and launch_canon use it.  The front builds: their number; build i's name (the kernel's spelling)
+// and out = stage (0 streaming, 1 rescue, 2 mixed), hash, aux, alpha, workgroup size, dynamic LDS bytes; whether it owns `mode`.
+extern "C" uint32_t emu_front_builds() { return N_FRONT_BUILDS; }
+extern "C" const char* emu_front_build(uint32_t i, uint32_t out[6])
+{
+    const FrontBuild& b = FRONT_BUILDS[i];
+    out[0] = b.stage; out[1] = b.hash; out[2] = b.aux; out[3] = b.alpha; out[4] = b.block; out[5] = b.lds;
+    return b.name;
+}
+extern "C" int emu_front_owns(uint32_t i, uint32_t mode) { return front_owns(FRONT_BUILDS[i], mode); }
+// the predicates themselves
+extern "C" int emu_stream_owns(uint32_t rows, uint32_t rpw, int hash, int aux, int alpha, uint32_t mode) { return stream_owns(rows, rpw, hash != 0, aux != 0, alpha != 0, mode); }
+extern "C" int emu_rescue_owns(int aux, int alpha, uint32_t mode) { return rescue_owns(aux != 0, alpha != 0, mode); }
+extern "C" int emu_mixed_owns(int nm, uint32_t mode) { return mixed_owns(nm != 0, mode); }
+extern "C" uint32_t emu_front_expected_mode(uint32_t host_mode, uint32_t seen) { return front_expected_mode(host_mode, seen); }
+// canon_front_plan: returns the number of launches, out[3 * k ..] = build, full size, grid of launch k (at most 8)
+extern "C" int emu_front_plan(int aux, int hash, uint32_t host_mode, uint32_t seen, uint32_t G, uint32_t nseg, uint32_t out[24])
+{
+    const FrontPlan p = canon_front_plan(aux != 0, hash != 0, host_mode, seen, G, nseg);
+    for (int k = 0; k < p.n; ++k) { out[3 * k] = p.e[k].build; out[3 * k + 1] = p.e[k].full; out[3 * k + 2] = p.e[k].grid; }
+    return p.n;
+}
+// batch_mode_of (canon_config.h), the rule the count kernel and host_batch both call
+extern "C" uint32_t emu_batch_mode_of(uint64_t two, uint64_t lng, uint64_t n, uint64_t bad, uint64_t sampled, uint64_t shortc, int hashed)
+{
+    return batch_mode_of(two, lng, n, bad, sampled, shortc, hashed != 0);
 }

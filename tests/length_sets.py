@@ -239,7 +239,11 @@ def mode_counts(lengths, data, offs):
 def expected_mode(lengths, data, offs, want_hash, aux):
     """The mode the device must report (bits 0..1: 1 one-word streaming builds, 2 two-word build, 3 mixed-length kernels; 4:
     MODE_ALPHA; 8: MODE_SHORT) for a batch whose outputs are `want_hash` and `aux` (index, strand or lmsr asked for)."""
-    c = mode_counts(lengths, data, offs)
+    return mode_of_counts(mode_counts(lengths, data, offs), want_hash, aux)
+
+
+def mode_of_counts(c, want_hash, aux):
+    """expected_mode's rule, from mode_counts' counts"""
     m = 3 if c["lng"] and c["lng"] * 8 >= c["n"] else 2 if c["two"] and c["two"] * 4 >= c["n"] else 1
     alpha = MODE_ALPHA if c["bad"] and c["bad"] * 16 >= c["sampled"] else 0
     if m == 2 and (alpha or (want_hash and not aux)):

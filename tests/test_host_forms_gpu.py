@@ -1,7 +1,7 @@
 """GPU: what the host-buffer entry points share -- the order and the text of what they refuse from the offsets alone, staging
 buffers that grow and are used again, and the life of a ctx that owns them.  The entry points: circkit_windows_gather,
 _windows_translate, _sketch_batch, _sketch_compare, _cluster_batch, _prealign_batch, _distance_pairs, _orfs_batch,
-_monomerize_batch, _monomers_batch, _uniq_batch and _fasta_write_text.  Every result is held against the unit's own yardstick
+_monomerize_batch, _monomers_batch, _uniq_batch, _fasta_write_text and (staging and lifecycle only) _canonicalize_batch.  Every result is held against the unit's own yardstick
 (tests/*_ref.py, oracle); the expected messages are literals."""
 import ctypes
 import functools
@@ -17,6 +17,7 @@ from tests import mono_ref
 from tests import monomers_ref as MR
 from tests import orfs_ref
 from tests import prealign_ref as PR
+from tests import seqsets
 from tests import sketch_ref as SR
 from tests import translate_ref as TR
 from tests import uniq_compact_ref as UR
@@ -336,8 +337,13 @@ def fasta_write_text(ctx, recs):
     return out
 
 
+def canonicalize_batch(ctx, recs):
+    got = ctx.canonicalize_batch(*pack(recs), want_bytes=True, want_index=True, want_strand=True, want_xxh3=True)
+    return tuple(got[f] for f in ("bytes", "index", "strand", "xxh3"))
+
+
 UNITS = (windows_gather, windows_translate, sketch_batch, sketch_compare, cluster_batch, prealign_batch, distance_pairs, orfs_batch, monomerize_batch,
-         monomers_batch, uniq_batch, fasta_write_text)
+         monomers_batch, uniq_batch, fasta_write_text, canonicalize_batch)
 
 
 @functools.lru_cache(maxsize=None)
@@ -393,6 +399,10 @@ def expected(unit, name):
             assert bad == 0
             out += (np.frombuffer(b"".join(recs_out), dtype=np.uint8), np.concatenate([[0], np.cumsum([len(r) for r in recs_out])]).astype(np.uint64))
         return out
+    if unit == "canonicalize_batch":
+        canon, hashes = O.canonicalize_batch(data, offs, True, True, threads=16)
+        per_record = [seqsets.expected(O, r) for r in recs]
+        return canon, np.array([idx for _, _, idx in per_record], dtype=np.uint32), np.array([st for _, st, _ in per_record], dtype=np.uint8), hashes
     raise KeyError(unit)
 
 
